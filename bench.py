@@ -13,6 +13,23 @@ elapsed, elapsed = MAX over ranks between barrier+synchronize fences.
 
 --alg impala / r2d2 run the same protocol on the other two learners
 (secondary benches; numbers recorded in profiles/).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, print ONE JSON result line. Anything beyond that belongs behind
+--full (off by default); today the plain run carries no such extras, so
+--full changes nothing yet.
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(the stepper's stats dict: loss, value, ...) and the updated fp32 master
+weights (params; a fixed seeded sample if large) as DIR/<name>.npy float32, so
+two builds can be compared output for output. Model init, replay prefill and
+the PER sampler are all seeded, and the Ape-X step's gradient and sum-tree
+kernels sum in a fixed order: same arguments -> same inputs and the same
+outputs up to the rounding of the two reported means (~2e-8 after 330 steps;
+tests/test_bench_cli.py::test_dump_outputs_reproducible_on_gpu). Two BUILDS
+whose kernels round differently still drift apart over a long run, because
+prioritized sampling amplifies last-bit differences: compare builds at a
+handful of steps.
 """
 
 from __future__ import annotations
@@ -146,6 +163,30 @@ def build_r2d2(cfg, device, rank, world, args):
     return learner, batch * T
 
 
+DUMP_BYTE_LIMIT = 64 << 20  # total budget for --dump-outputs
+
+
+def dump_outputs(out_dir: str, stats) -> None:
+    """Write the last timed step's return value (dict of tensors) as
+    <out_dir>/<name>.npy float32. An output too big for its share of the
+    64 MB budget is reduced to a fixed, seeded sample of its elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        str(k): v.detach().to("cpu", torch.float32).numpy()
+        if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)
+        for k, v in dict(stats).items()
+    }
+    share = DUMP_BYTE_LIMIT // max(len(arrays), 1) // 4  # elements per array
+    for name, a in arrays.items():
+        if a.size > share:
+            pick = np.random.default_rng(0).choice(a.size, share, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -172,7 +213,18 @@ def main():
     ap.add_argument("--burn-in", type=int, default=None,
                     help="R2D2 burn-in override (BASELINE config 4 = 40)")
     ap.add_argument("--transport-dir", default=None)
+    ap.add_argument("--seed", type=int, default=0,
+                    help="model-init seed (replay prefill and PER sampler "
+                         "carry fixed seeds of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure "
+                         "(secondary measurements and checks); a plain run "
+                         "has none today, so this adds nothing yet")
     args = ap.parse_args()
+    torch.manual_seed(args.seed)
 
     # cap intra-op threads: the default (ncores) oversubscribes the
     # box against the actor fleet and the ingest pack
@@ -294,11 +346,23 @@ def main():
         stepper()
     barrier_sync()
     ingested0 = learner.ingested_total if args.with_actors else 0
+    count0 = learner.step_count  # the learner's own count of steps taken
     t0 = time.perf_counter()
+    last_stats = None
     for i in range(args.steps):
-        stepper()
+        last_stats = stepper()
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    steps_run = learner.step_count - count0
+    if args.dump_outputs and rank == 0 and last_stats is not None:
+        # right after the fence: a graphed stepper returns static buffers
+        # that the next replay would overwrite. Two scalar means are a weak
+        # fingerprint, so the step's other product goes along: the updated
+        # fp32 master weights the caller holds through the learner.
+        with torch.no_grad():
+            params = torch.cat([p.detach().float().reshape(-1)
+                                for p in learner.model.parameters()])
+        dump_outputs(args.dump_outputs, dict(last_stats, params=params))
     ingested = (learner.ingested_total - ingested0) if args.with_actors else 0
     if args.with_actors > 0:
         drops = (learner.transport.total_drops()
@@ -336,6 +400,7 @@ def main():
             "unit": "frames/s",
             "n_gpus": max(n_gpus, 1),
             "steps": args.steps,
+            "steps_run": steps_run,  # counted by the learner, not echoed
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True,

@@ -4,7 +4,7 @@ A from-scratch framework with the capabilities of seungju-k1m/Distributed_RL
 (Ape-X DQN, R2D2, IMPALA on Atari-shaped observations), re-architected for
 AMD Instinct MI355X (gfx950 / CDNA4):
 
-* GPU-resident lock-free prioritized replay (sum-tree in HBM3E) instead of a
+* GPU-resident prioritized replay (sum-tree in HBM3E) instead of a
   Redis + host-thread replay pipeline,
 * hand-written HIP kernels for the learner hot path (dequant, fused TD loss,
   V-trace scan, value rescaling, sequence priorities, grad clip),

@@ -157,12 +157,12 @@ class _FusedConvFn(torch.autograd.Function):
         )
         gw = gb = None
         if use_own_wrw:
-            # hand-written MFMA weight-grad (conv_mfma.hip): fp32 workspace
-            # accumulated by atomics, cast to the bf16 channels_last grad.
-            # single zero-fill for both workspaces (one FillFunctor launch
-            # instead of two — these run every step inside the graph)
+            # hand-written MFMA weight-grad (conv_mfma.hip): per-m-slice
+            # partials summed in a fixed order (reproducible) into the fp32
+            # workspaces, every element of which the op writes (no
+            # zero-fill); cast to the bf16 channels_last grad here
             K = KH * KW * C
-            flat_ws = torch.zeros(COUT * (K + 1), dtype=torch.float32,
+            flat_ws = torch.empty(COUT * (K + 1), dtype=torch.float32,
                                   device=x.device)
             ws = flat_ws[: COUT * K].view(COUT, K)
             gb_ws = (flat_ws[COUT * K :] if need_b

@@ -384,7 +384,8 @@ void register_conv(pybind11::module_& m) {
 // sample dim m, so both operands need m-major fragments: we stage 32-sample
 // chunks into LDS TRANSPOSED (scalar b16 writes, padded rows) so fragment
 // reads are clean b128s, MFMA accumulates COUT x 64-kelem tiles, and each
-// block atomicAdds its partial into an fp32 workspace.
+// block writes its partial to its m-slice's fp32 plane (summed in a fixed
+// order by wrw_reduce_kernel).
 //   grid = (K/64 ktiles, MB m-slices); block = 4 waves; wave w owns the
 //   16-kelem column block w.
 // ===========================================================================
@@ -392,6 +393,9 @@ void register_conv(pybind11::module_& m) {
 namespace {
 
 constexpr int kPadM = 8;  // row pad (elements) for the staged tiles
+// wrw partial planes are COUT*K floats = an even number of 256 B lines; one
+// extra line makes the plane stride odd so planes spread over memory channels
+constexpr int kPlanePad = 64;
 
 typedef __bf16 v4bf_w __attribute__((ext_vector_type(4)));
 
@@ -421,7 +425,7 @@ template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8IN>
 __global__ __launch_bounds__(256) void conv_wrw_kernel(
     const void* __restrict__ in_v,      // (N,H,W,C) NHWC u8/bf16
     const __bf16* __restrict__ gout,    // (M, COUT) = NHWC grad (relu-masked)
-    float* __restrict__ gw_ws,          // (COUT, K) fp32, pre-zeroed
+    float* __restrict__ gw_part,        // (mblocks, COUT, K) fp32 partials
     int batch, int mblocks) {
   using G = ConvGeom<H, W, C, KH, KW, S, COUT, U8IN>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -522,15 +526,80 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(
     __syncthreads();
   }
 
-  // ---- epilogue: atomic-accumulate partials into the fp32 workspace
+  // ---- epilogue: this m-slice's partial goes to its own (COUT, K) plane;
+  // wrw_reduce_kernel sums the planes in a fixed order, so the result does
+  // not depend on block scheduling (float atomics did: run-to-run jitter in
+  // the last bit, which PER sampling amplifies into different batches)
+  float* plane = gw_part + (int64_t)mb * (COUT * G::K + kPlanePad);
   const int kout = ktile * 64 + wave * 16 + (lane & 15);
 #pragma unroll
   for (int cb = 0; cb < CBLK; ++cb)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int cout = cb * 16 + (lane >> 4) * 4 + r;
-      atomicAdd(&gw_ws[(int64_t)cout * G::K + kout], acc[cb][r]);
+      plane[(int64_t)cout * G::K + kout] = acc[cb][r];
     }
+}
+
+// Ordered sum of the per-m-slice planes: block = 64 elements (16 lanes x
+// float4) x 16 plane groups; group g adds planes g, g+16, ... in order, then
+// the group sums fold in group order. The last block (bias == true launches one
+// extra) folds the bias-grad partials of colsum_bf16_kernel the same way.
+__global__ __launch_bounds__(256) void wrw_reduce_kernel(
+    const float* __restrict__ part, int planes, int n_elem,
+    float* __restrict__ out, const float* __restrict__ b_part, int b_planes,
+    int cout, float* __restrict__ b_out) {
+  __shared__ __attribute__((aligned(16))) float sh4_raw[256 * 4];
+  float* sh = sh4_raw;
+  const int tid = threadIdx.x;
+  const int e_blocks = (n_elem + 63) / 64;
+  if ((int)blockIdx.x < e_blocks) {
+    // 16 lanes x float4 = 64 elements; 16 plane groups (n_elem % 64 == 0)
+    const int e4 = blockIdx.x * 64 + (tid & 15) * 4;
+    const int g = tid >> 4;
+    float4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+    // four loads in flight per lane (the pass is latency-bound otherwise);
+    // the adds stay in plane order g, g+16, g+32, ...
+    const float4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int p = g; p < planes; p += 64) {
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int pu = p + 16 * u;
+        v[u] = pu < planes ? *reinterpret_cast<const float4*>(
+                                 part + (int64_t)pu * (n_elem + kPlanePad) + e4)
+                           : zero;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w;
+      }
+    }
+    float4* sh4 = reinterpret_cast<float4*>(sh4_raw);
+    sh4[tid] = s;
+    __syncthreads();
+    if (tid < 16) {
+      float4 t = sh4[tid];
+      for (int k = 1; k < 16; ++k) {  // fixed fold order over the groups
+        const float4 v = sh4[k * 16 + tid];
+        t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+      }
+      *reinterpret_cast<float4*>(out + e4) = t;
+    }
+  } else {
+    // bias fold: thread (g, c) adds block partials g, g+G, ...; G = 256/cout
+    const int G = 256 / cout;
+    const int c = tid % cout, g = tid / cout;
+    float s = 0.0f;
+    for (int p = g; p < b_planes; p += G) s += b_part[p * cout + c];
+    sh[tid] = s;
+    __syncthreads();
+    if (tid < cout) {
+      float t = 0.0f;
+      for (int k = 0; k < G; ++k) t += sh[k * cout + tid];
+      b_out[tid] = t;
+    }
+  }
 }
 
 struct WrwLaunch {
@@ -563,7 +632,8 @@ static const WrwLaunch kWrwLaunches[] = {
 
 // bias grad: column sum of the (M, COUT) relu-masked gout — torch's
 // strided bf16 reduce on channels_last costs ~11 us; this is one pass with
-// a block-level LDS reduction and COUT atomics per block.
+// an ordered block-level LDS reduction; each block writes its COUT partial
+// sums to out[block][COUT] and wrw_reduce_kernel folds the blocks in order.
 template <int COUT>
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(
     const __bf16* __restrict__ x, int64_t M, float* __restrict__ out) {
@@ -573,14 +643,11 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(
   // and its 8 fp32 accumulators map to fixed columns. (Scalar 2 B loads
   // measured only ~0.5 TB/s — load-width bound.)
   typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-  __shared__ float sh[COUT];
+  __shared__ float sh[256 * 8];
   const int tid = threadIdx.x;
-  for (int c = tid; c < COUT; c += 256) sh[c] = 0.0f;
-  __syncthreads();
   const int64_t nchunk = M * COUT / 8;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + tid;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int phase = (int)(((uint64_t)i * 8) % COUT);
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const bf8* __restrict__ x8 = (const bf8*)x;
   for (; i < nchunk; i += stride) {
@@ -588,10 +655,17 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] += (float)v[j];
   }
+  // ordered block reduction (no float atomics: fixed summation order).
+  // phase == (tid * 8) % COUT because gridDim-independent 2048 % COUT == 0,
+  // so column c is held by threads t = c/8 + n * (COUT/8), slot c % 8.
 #pragma unroll
-  for (int j = 0; j < 8; ++j) atomicAdd(&sh[phase + j], acc[j]);
+  for (int j = 0; j < 8; ++j) sh[tid * 8 + j] = acc[j];
   __syncthreads();
-  if (tid < COUT) atomicAdd(&out[tid], sh[tid]);
+  if (tid < COUT) {
+    float s = 0.0f;
+    for (int t = tid >> 3; t < 256; t += COUT / 8) s += sh[t * 8 + (tid & 7)];
+    out[(int64_t)blockIdx.x * COUT + tid] = s;  // per-block partial
+  }
 }
 
 }  // namespace
@@ -606,7 +680,8 @@ bool conv_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
 }
 
 // in: (N,C,H,W) channels_last u8/bf16; gout: (N,COUT,P,Q) channels_last bf16
-// (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 pre-zeroed.
+// (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 and gb_ws: (COUT) fp32
+// (or empty), both fully overwritten.
 void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
               torch::Tensor gb_ws, int64_t stride) {
   TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast));
@@ -634,36 +709,53 @@ void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
   // scale the m-grid with the batch: R2D2/IMPALA run 8-20x Ape-X's row
   // count through the same kernel (conv1 wrw measured 139 us at 1.02M
   // rows with 512 blocks = 250 serial chunks per block)
-  int mb = (n_chunks > 8192 ? 2048 : 512) / L->ktiles;  // 4096 A/B'd worse (atomics)
+  int mb = (n_chunks > 8192 ? 2048 : 512) / L->ktiles;  // every m-slice costs one partial plane of write + read traffic
   if (mb > n_chunks) mb = n_chunks;
   if (mb < 1) mb = 1;
-  hipLaunchKernelGGL(L->fn, dim3(L->ktiles, mb), dim3(256), L->lds_bytes,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
+  auto st = (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
+  const int n_elem = (int)gw_ws.numel();
+  TORCH_CHECK(n_elem == COUT * L->ktiles * 64, "gw_ws shape mismatch");
+  // per-m-slice partial planes (every (ktile, m-slice) block writes its
+  // whole 64 x COUT tile, so no zero-fill) + ordered reduction
+  auto part = torch::empty({(int64_t)mb, (int64_t)n_elem + kPlanePad},
+                           gw_ws.options());
+  hipLaunchKernelGGL(L->fn, dim3(L->ktiles, mb), dim3(256), L->lds_bytes, st,
                      (const void*)in.data_ptr(), (const __bf16*)gout.data_ptr(),
-                     gw_ws.data_ptr<float>(), N, mb);
-  if (gb_ws.defined() && gb_ws.numel() > 0) {
+                     part.data_ptr<float>(), N, mb);
+  const bool bias = gb_ws.defined() && gb_ws.numel() > 0;
+  constexpr int kColsumBlocks = 256;
+  torch::Tensor b_part;
+  if (bias) {
+    TORCH_CHECK(gb_ws.numel() == COUT && gb_ws.scalar_type() == torch::kFloat32);
+    b_part = torch::empty({(int64_t)kColsumBlocks, (int64_t)COUT},
+                          gw_ws.options());
     const int64_t Mrows = (int64_t)N * P * Q;
-    auto st = (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
     switch (COUT) {
       case 16:
-        hipLaunchKernelGGL(colsum_bf16_kernel<16>, dim3(256), dim3(256), 0, st,
-                           (const __bf16*)gout.data_ptr(), Mrows,
-                           gb_ws.data_ptr<float>());
+        hipLaunchKernelGGL(colsum_bf16_kernel<16>, dim3(kColsumBlocks),
+                           dim3(256), 0, st, (const __bf16*)gout.data_ptr(),
+                           Mrows, b_part.data_ptr<float>());
         break;
       case 32:
-        hipLaunchKernelGGL(colsum_bf16_kernel<32>, dim3(256), dim3(256), 0, st,
-                           (const __bf16*)gout.data_ptr(), Mrows,
-                           gb_ws.data_ptr<float>());
+        hipLaunchKernelGGL(colsum_bf16_kernel<32>, dim3(kColsumBlocks),
+                           dim3(256), 0, st, (const __bf16*)gout.data_ptr(),
+                           Mrows, b_part.data_ptr<float>());
         break;
       case 64:
-        hipLaunchKernelGGL(colsum_bf16_kernel<64>, dim3(256), dim3(256), 0, st,
-                           (const __bf16*)gout.data_ptr(), Mrows,
-                           gb_ws.data_ptr<float>());
+        hipLaunchKernelGGL(colsum_bf16_kernel<64>, dim3(kColsumBlocks),
+                           dim3(256), 0, st, (const __bf16*)gout.data_ptr(),
+                           Mrows, b_part.data_ptr<float>());
         break;
       default:
         TORCH_CHECK(false, "no colsum instantiation for COUT=", COUT);
     }
   }
+  const int e_blocks = (n_elem + 63) / 64;
+  hipLaunchKernelGGL(wrw_reduce_kernel, dim3(e_blocks + (bias ? 1 : 0)),
+                     dim3(256), 0, st, (const float*)part.data_ptr<float>(), mb,
+                     n_elem, gw_ws.data_ptr<float>(),
+                     bias ? (const float*)b_part.data_ptr<float>() : nullptr,
+                     kColsumBlocks, COUT, bias ? gb_ws.data_ptr<float>() : nullptr);
 }
 
 // tr16 semantics probe: fill LDS with 0..511, each lane passes base +

@@ -12,8 +12,8 @@
 //
 // Design notes (CDNA4): wave64; block sizes are multiples of 64; elementwise
 // kernels are vectorized to >=8 B/lane and grid-stride-capped (guide §6 G11/G13);
-// the sum-tree is lock-free — leaf swap via atomicExch, ancestor fix-up via
-// atomicAdd deltas, so concurrent ingest/update batches compose correctly.
+// the sum-tree update stores leaves and recomputes the touched inner nodes
+// from their children (no float atomics: reproducible node values).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -90,15 +90,15 @@ __global__ void dequant_u8_bf16_nhwc_c4_kernel(const uint8_t* __restrict__ in,
 }
 
 // ---------------------------------------------------------------------------
-// K10: lock-free sum-tree. Layout: float tree[2P], P = pow2 >= capacity,
+// K10: sum-tree. Layout: float tree[2P], P = pow2 >= capacity,
 // root tree[1], leaves tree[P + i]. tree[1] is the running total priority.
 // ---------------------------------------------------------------------------
 
-// Two-phase update kills root contention: phase 1 propagates atomic deltas
-// only through the wide bottom levels (node >= TOP, where random leaves
-// rarely collide); phase 2 (one block) deterministically rebuilds the top
-// TOP-1 nodes level by level. 512 concurrent updates on a 2^17 tree went
-// 136us -> ~6us with this split (profiles/).
+// Three-phase update, no float atomics: phase 1 stores the leaves; phase 2
+// rebuilds the touched subtrees below the TOP level (node >= TOP), one block
+// per subtree; phase 3 (one block) rebuilds the top TOP-1 nodes level by
+// level. Every inner node is the sum of its two children, computed in a
+// fixed order, so the tree (and the sampled batch) is reproducible.
 constexpr int64_t kTreeTop = 2048;
 
 __global__ void sumtree_update_kernel(float* __restrict__ tree,
@@ -107,13 +107,36 @@ __global__ void sumtree_update_kernel(float* __restrict__ tree,
                                       int m, int64_t P, int64_t top) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
-  int64_t leaf = P + idx[i];
-  float newp = prio[i];
-  float old = atomicExch(&tree[leaf], newp);  // duplicate-safe: each swap sees
-  float delta = newp - old;                   // a consistent predecessor value
-  if (delta == 0.0f) return;
-  for (int64_t node = leaf >> 1; node >= top; node >>= 1)
-    atomicAdd(&tree[node], delta);
+  // leaves only; every inner node is recomputed from its children by the
+  // two rebuild kernels below, so node values are exact child sums in a
+  // fixed order (atomicAdd deltas left order-dependent last bits in the
+  // nodes, which the inverse-CDF descent turns into different samples)
+  // Duplicate indices in one call: which entry lands last is NOT defined
+  // (as before). Callers only ever pass duplicates with equal priorities (a
+  // leaf sampled twice gets the same TD error; ingest indices are unique),
+  // and the rebuilds read the leaf afterwards, so the tree stays consistent
+  // with whatever value won. The exchange is kept from the old kernel.
+  atomicExch(&tree[P + idx[i]], prio[i]);
+}
+
+// Rebuild the levels between the leaves and the `top` level: block b owns
+// the subtree rooted at node r (depth-d nodes are (r << d) + j) and sums it
+// bottom-up. With idx != nullptr block b rebuilds only the subtree that
+// holds leaf idx[b] (blocks that share a subtree write identical values);
+// with idx == nullptr block b rebuilds subtree top + b.
+__global__ void sumtree_rebuild_mid_kernel(float* __restrict__ tree,
+                                           const int64_t* __restrict__ idx,
+                                           int64_t P, int64_t top, int depth) {
+  const int64_t r = idx ? ((P + idx[blockIdx.x]) >> depth)
+                        : (top + (int64_t)blockIdx.x);
+  for (int d = depth - 1; d >= 0; --d) {
+    const int64_t base = r << d;
+    for (int64_t j = threadIdx.x; j < ((int64_t)1 << d); j += blockDim.x) {
+      const int64_t n = base + j;
+      tree[n] = tree[2 * n] + tree[2 * n + 1];
+    }
+    __syncthreads();
+  }
 }
 
 __global__ void sumtree_rebuild_top_kernel(float* __restrict__ tree,
@@ -499,6 +522,19 @@ void sumtree_update(torch::Tensor tree, torch::Tensor idx, torch::Tensor prio,
   hipLaunchKernelGGL(sumtree_update_kernel, dim3(ceil_div(m, kBlock)), dim3(kBlock),
                      0, cur_stream(), tree.data_ptr<float>(),
                      idx.data_ptr<int64_t>(), prio.data_ptr<float>(), m, P, top);
+  int depth = 0;  // levels between the `top` level and the leaves
+  while ((top << depth) < P) ++depth;
+  if (depth > 0) {
+    // few updates: one block per touched leaf's subtree; many (ingest
+    // pushes): every subtree once
+    const bool by_idx = (int64_t)m < top;
+    const int threads = (P / top) <= 128 ? 64 : 256;
+    hipLaunchKernelGGL(sumtree_rebuild_mid_kernel,
+                       dim3(by_idx ? m : (int)top), dim3(threads), 0,
+                       cur_stream(), tree.data_ptr<float>(),
+                       by_idx ? idx.data_ptr<int64_t>() : nullptr, P, top,
+                       depth);
+  }
   hipLaunchKernelGGL(sumtree_rebuild_top_kernel, dim3(1), dim3(1024), 0,
                      cur_stream(), tree.data_ptr<float>(), top);
 }
@@ -753,7 +789,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_conv(m);
   m.def("dequant", &dequant, "u8 -> bf16/f32 /255 (K1)");
   m.def("dequant_nhwc", &dequant_nhwc, "u8 NCHW -> bf16 NHWC /255 (K1)");
-  m.def("sumtree_update", &sumtree_update, "lock-free sum-tree leaf update (K10)");
+  m.def("sumtree_update", &sumtree_update, "sum-tree leaf update + ordered subtree/top rebuild (K10); calls on one "
+        "tree must be stream-ordered");
   m.def("sumtree_sample", &sumtree_sample, "stratified sum-tree descent (K10)");
   m.def("leaf_min_pos", &leaf_min_pos, "min positive leaf priority (K10)");
   m.def("per_weights", &per_weights, "PER IS weights (K10)");

@@ -1,11 +1,13 @@
-"""HBM3E-resident lock-free sum-tree PER — the production learner replay.
+"""HBM3E-resident sum-tree PER — the production learner replay.
 
 Replaces the reference's Redis-list + host-thread replay pipeline
 (APE_X/ReplayMemory.py:19-167): experiences live in device memory as typed
 columns (288 GB HBM3E per MI355X), priorities live in a binary sum-tree
-(float[2P], P = next pow2 of capacity) updated by atomicExch/atomicAdd
-kernels so concurrent ingest (side stream) and priority updates (compute
-stream) compose without locks. Sampling is a stratified inverse-CDF descent,
+(float[2P], P = next pow2 of capacity): an update stores the leaves and
+recomputes the touched inner nodes from their children, so node values are
+exact child sums in a fixed order and a run is reproducible. Ingest (side
+stream) and priority updates (compute stream) must be stream-ordered against
+each other, as the learners do. Sampling is a stratified inverse-CDF descent,
 one lane per sample. All ops are fixed-shape device kernels -> the whole
 train step is hipGraph-capturable.
 """

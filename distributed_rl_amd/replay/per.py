@@ -12,7 +12,7 @@ and the inferred ``baseline.PER`` surface):
 Two implementations share this interface:
   * TorchPER (this file): pure torch ops; runs on CPU (tests, GPU-less actors)
     and is the numerics oracle for the HIP path.
-  * HipSumTreePER (gpu_per.py): lock-free sum-tree in HBM3E driven by the
+  * HipSumTreePER (gpu_per.py): sum-tree in HBM3E driven by the
     hand-written gfx950 kernels in ops/hip/ — the production learner path.
 """
 
