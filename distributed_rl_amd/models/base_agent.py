@@ -239,6 +239,54 @@ class LSTMNET(nn.Module):
         return out
 
 
+def _resconv_gate() -> bool:
+    """DRL_OWN_RESCONV: '1' forces the hand-written 3x3 pad-1 conv path on,
+    '0' forces it off; unset takes the measured default
+    (profiles/r03_resnet_conv.md)."""
+    import os as _os
+
+    v = _os.environ.get("DRL_OWN_RESCONV")
+    if v is None or v == "":
+        return _RESCONV_DEFAULT
+    return v == "1"
+
+
+# default of the DRL_OWN_RESCONV gate, decided by the A/B in
+# profiles/r03_resnet_conv.md: 6.508 vs 7.688 ms/step median against the
+# library convs, repeat spread 0.03 ms -> on
+_RESCONV_DEFAULT = True
+
+
+def _resconv_ok(x: torch.Tensor, *convs: nn.Conv2d) -> bool:
+    """Fused 3x3 pad-1 path (ops/hip/conv_mfma.hip conv3x3p1_fwd_kernel):
+    CUDA bf16 channels_last input, bf16 weights, every conv's geometry
+    covered, gate on."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
+        return False
+    if not _resconv_gate():
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        return False
+    from .. import ops as _ops
+
+    H, W = x.shape[2], x.shape[3]
+    for conv in convs:
+        w = conv.weight
+        if w.dtype != torch.bfloat16 or tuple(w.shape[2:]) != (3, 3):
+            return False
+        if conv.stride != (1, 1) or conv.padding != (1, 1) \
+                or conv.dilation != (1, 1) or conv.groups != 1:
+            return False
+        # 16-byte weight pieces: a weight viewed out of a flat parameter
+        # buffer may sit at any 2-byte offset
+        if w.data_ptr() % 16 or not w.is_contiguous(
+                memory_format=torch.channels_last):
+            return False
+        if not _ops.conv3x3_supported(H, W, w.shape[1], w.shape[0]):
+            return False
+    return True
+
+
 class ResidualBlock(nn.Module):
     def __init__(self, ch: int):
         super().__init__()
@@ -246,6 +294,14 @@ class ResidualBlock(nn.Module):
         self.c2 = nn.Conv2d(ch, ch, 3, padding=1)
 
     def forward(self, x):
+        if _resconv_ok(x, self.c1, self.c2):
+            from .. import ops as _ops
+
+            # c1 reads relu(x) and writes relu(c1(.)); c2 adds the raw x
+            y = _ops.fused_conv3x3(x, self.c1.weight, self.c1.bias,
+                                   relu_in=True, relu_out=True)
+            return _ops.fused_conv3x3(y, self.c2.weight, self.c2.bias,
+                                      residual=x)
         y = self.c1(torch.relu(x))
         y = self.c2(torch.relu(y))
         return x + y
@@ -256,7 +312,12 @@ class ImpalaResNet(nn.Module):
     conv3x3 -> maxpool3x3 s2 -> nBlocks residual blocks; final ReLU+flatten.
     Used by cfg/impala_resnet.json (BASELINE.json config 3: 'IMPALA deep
     ResNet V-trace, 8x MI355X learner-DP'). Beyond the reference repo's
-    capability (it only ships the shallow torso) — netCat: IMPALA_RESNET."""
+    capability (it only ships the shallow torso) — netCat: IMPALA_RESNET.
+
+    On bf16 channels_last GPU input the 3x3 pad-1 convs whose geometry the
+    hand-written kernel covers (everything but the first, C=4 conv at
+    84x84) run through ops.fused_conv3x3 when DRL_OWN_RESCONV allows;
+    pooling, the first conv and the final ReLU+flatten stay in torch."""
 
     def __init__(self, cfg: Dict[str, Any]):
         super().__init__()
@@ -274,7 +335,18 @@ class ImpalaResNet(nn.Module):
         self.body = nn.Sequential(*sections)
 
     def forward(self, x):
-        y = self.body(x)
+        if x.is_cuda and x.dtype == torch.bfloat16 and _resconv_gate():
+            from .. import ops as _ops
+
+            y = x
+            for layer in self.body:
+                if isinstance(layer, nn.Conv2d) and _resconv_ok(y, layer):
+                    # section-entry conv: no flags
+                    y = _ops.fused_conv3x3(y, layer.weight, layer.bias)
+                else:
+                    y = layer(y)
+        else:
+            y = self.body(x)
         y = torch.relu(y)
         return torch.flatten(y, 1)
 

@@ -220,6 +220,85 @@ def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
     return _FusedConvFn.apply(x, weight, bias, stride, chw_out)
 
 
+# ---------------------------------------------------------------------------
+# K2b — fused MFMA 3x3 stride-1 pad-1 conv for the IMPALA-ResNet torso
+# (relu_in / bias / residual / relu_out fused; aten backward)
+# ---------------------------------------------------------------------------
+
+
+def conv3x3_supported(H, W, C, COUT) -> bool:
+    ext = hip_ext(required=False)
+    return ext is not None and hasattr(ext, "conv3x3p1_supported") and \
+        bool(ext.conv3x3p1_supported(H, W, C, COUT))
+
+
+class _FusedConv3x3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, relu_in, relu_out):
+        ext = hip_ext()
+        N, _, H, W = x.shape
+        COUT = weight.shape[0]
+        empty = torch.empty(0, device=x.device, dtype=torch.bfloat16)
+        out = torch.empty(
+            N, COUT, H, W, dtype=torch.bfloat16, device=x.device,
+            memory_format=torch.channels_last,
+        )
+        ext.conv3x3p1_fwd(x, weight, bias if bias is not None else empty,
+                          residual if residual is not None else empty, out,
+                          relu_in, relu_out)
+        # out is only needed for the relu_out mask
+        ctx.save_for_backward(x, weight, out if relu_out else None)
+        ctx.has_bias = bias is not None
+        ctx.relu_in = relu_in
+        ctx.relu_out = relu_out
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, weight, out = ctx.saved_tensors
+        ext = hip_ext()
+        COUT = weight.shape[0]
+        if not gout.is_contiguous(memory_format=torch.channels_last):
+            gout = gout.contiguous(memory_format=torch.channels_last)
+        if ctx.relu_out:
+            masked = torch.empty_like(gout)
+            ext.relu_mask_bwd(gout, out, masked)
+            gout = masked
+        need_x = ctx.needs_input_grad[0]
+        need_w = ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        gres = gout if ctx.needs_input_grad[3] else None
+        gx = gw = gb = None
+        if need_x or need_w or need_b:
+            # weight- and input-gradient kernels for the padded geometries
+            # are the follow-up: the library runs them
+            gx, gw, gb = torch.ops.aten.convolution_backward(
+                gout, torch.relu(x) if ctx.relu_in else x, weight,
+                [COUT] if ctx.has_bias else None,
+                [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                [need_x, need_w, need_b],
+            )
+            if need_x and ctx.relu_in:
+                if not gx.is_contiguous(memory_format=torch.channels_last):
+                    gx = gx.contiguous(memory_format=torch.channels_last)
+                masked = torch.empty_like(gx)
+                ext.relu_mask_bwd(gx, x, masked)
+                gx = masked
+        return (gx if need_x else None), gw, gb, gres, None, None
+
+
+def fused_conv3x3(x, weight, bias, *, relu_in: bool = False,
+                  relu_out: bool = False, residual=None):
+    """3x3 stride-1 pad-1 conv with the residual-block fusions:
+    ``relu?(conv(relu?(x)) + bias + residual?)``. Device tensors must be bf16
+    channels_last at a geometry conv3x3_supported() covers; CPU tensors take
+    the eager reference."""
+    if _use_hip(x):
+        return _FusedConv3x3Fn.apply(x, weight, bias, residual, bool(relu_in),
+                                     bool(relu_out))
+    return torch_ref.conv3x3_res(x, weight, bias, relu_in, relu_out, residual)
+
+
 def conv_chw_supported(H, W, C, KH, KW, S, COUT) -> bool:
     ext = hip_ext(required=False)
     return ext is not None and hasattr(ext, "conv_fwd_chw_supported") and \

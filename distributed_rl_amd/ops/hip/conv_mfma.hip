@@ -354,6 +354,10 @@ void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                  torch::Tensor out);  // defined below
 bool linear_relu_supported(int64_t K, int64_t N);
 void tr16_probe(torch::Tensor out, int64_t mode);
+void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
+                   torch::Tensor residual, torch::Tensor out, bool relu_in,
+                   bool relu_out);  // defined below
+bool conv3x3p1_supported(int64_t H, int64_t W, int64_t C, int64_t COUT);
 
 void register_conv(pybind11::module_& m) {
   m.def("conv_fwd", &conv_fwd,
@@ -375,6 +379,10 @@ void register_conv(pybind11::module_& m) {
         "fused Linear+bias+ReLU fwd (own MFMA GEMM, LDS-staged W)");
   m.def("linear_relu_supported", &linear_relu_supported);
   m.def("tr16_probe", &tr16_probe);
+  m.def("conv3x3p1_fwd", &conv3x3p1_fwd,
+        "MFMA 3x3 s1 pad-1 NHWC bf16 conv fwd (+relu_in, bias, residual, "
+        "relu_out)");
+  m.def("conv3x3p1_supported", &conv3x3p1_supported);
 }
 
 // ===========================================================================
@@ -1166,4 +1174,292 @@ void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                      0, (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
                      (const __bf16*)x.data_ptr(), (const __bf16*)w.data_ptr(),
                      bp, (__bf16*)out.data_ptr(), M);
+}
+
+// ===========================================================================
+// 3x3 stride-1 pad-1 forward for the IMPALA-ResNet torso
+// (cfg/impala_resnet.json: 84x84 input, channels 16/32/32 -> 42x42x16,
+// 42x42x16->32, 21x21x32, 11x11x32). Same implicit-GEMM view, LDS-staged
+// weights and 16x16x32 bf16 fragment maps as conv_fwd_kernel, plus:
+//   * padding: K order is (kh, kw, c) = the channels_last weight viewed as
+//     (COUT, 9C). A lane's 8-element piece lies inside one tap (8 | C):
+//     tap = kelem / C, (dy, dx) = (tap/3 - 1, tap%3 - 1). A piece whose tap
+//     falls outside the image (or past tap 8, C=16 tail) is exact zeros and
+//     is never loaded — the address is not dereferenced.
+//   * C=32: K=288 = 9 chunks, one tap each. C=16: K=144 padded to 160 in
+//     LDS (columns 144..159 zero) = 5 chunks of two taps.
+//   * operands swapped in the MFMA (weights as A, im2col rows as B — the
+//     per-lane loads are identical since both maps are [l&15][8*(l>>4)+j]):
+//     the accumulator then holds out^T, i.e. 4 consecutive couts of one
+//     output row per lane -> 8-byte residual loads and output stores.
+//   * fusions: relu_in on the A pieces as they are loaded; epilogue in f32:
+//     + bias, + residual, ReLU (relu_out), round to bf16.
+// ===========================================================================
+namespace {
+
+using s16x8 = __attribute__((ext_vector_type(8))) short;
+using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+
+template <int C, int COUT>
+struct Conv3Geom {
+  static constexpr int K = 9 * C;
+  static constexpr int KP = (K + 31) / 32 * 32;  // 288 (C=32), 160 (C=16)
+  static constexpr int KCHUNKS = KP / 32;
+  // row pad chosen per geometry for the kPad rule: (row_elems*2) % 256 in
+  // {64, 192}. 288 and 160 both land on 64 with no pad at all.
+  static constexpr int PAD = 0;
+  static constexpr int LDS_ROW = KP + PAD;
+  static constexpr int LDS_ELEMS = COUT * LDS_ROW;
+  static constexpr int LDS_BYTES = (LDS_ELEMS + COUT) * 2;  // weights + bias
+  static_assert(C % 8 == 0, "an 8-element piece must not straddle a tap");
+  static_assert((LDS_ROW * 2) % 256 == 64 || (LDS_ROW * 2) % 256 == 192,
+                "LDS row stride breaks the bank-spread rule");
+  static_assert(LDS_ROW % 8 == 0, "LDS rows must stay 16-byte aligned");
+  static_assert(COUT % 16 == 0, "COUT must tile by 16");
+  static_assert(COUT <= 64, "bias staging uses the first COUT threads");
+};
+
+template <int H, int W, int C, int COUT, int WAVES, int RPW>
+__global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
+    const __bf16* __restrict__ in,        // (N,H,W,C) NHWC
+    const __bf16* __restrict__ weight,    // (COUT, 9C) = (cout, kh, kw, c)
+    const __bf16* __restrict__ bias,      // (COUT), may be null
+    const __bf16* __restrict__ residual,  // (N,H,W,COUT), may be null
+    __bf16* __restrict__ out,             // (N,H,W,COUT)
+    int batch, int relu_in, int relu_out) {
+  using G = Conv3Geom<C, COUT>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* wlds = reinterpret_cast<__bf16*>(smem);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+
+  // ---- stage weights into LDS: [cout][KP + pad], K tail zero-filled ----
+  for (int base = tid * 8; base < COUT * G::KP; base += WAVES * 64 * 8) {
+    const int co = base / G::KP;
+    const int k = base - co * G::KP;
+    bf16x8 v = {};
+    if (k < G::K) v = *reinterpret_cast<const bf16x8*>(weight + co * G::K + k);
+    *reinterpret_cast<bf16x8*>(wlds + co * G::LDS_ROW + k) = v;
+  }
+  // bias rides along behind the weights (a bias living in a flat parameter
+  // buffer is only 2-byte aligned: scalar loads here, one b64 read later)
+  __bf16* blds = wlds + G::LDS_ELEMS;
+  if (tid < COUT) blds[tid] = bias ? bias[tid] : (__bf16)0.0f;
+  __syncthreads();
+
+  const int M = batch * H * W;
+  const int row0 = (blockIdx.x * WAVES + wave) * RPW;
+  if (row0 >= M) return;
+  constexpr int RFRAG = RPW / 16;
+  constexpr int NFRAG = COUT / 16;
+  // per-lane im2col row, one per row-fragment (clamped for the ragged tail)
+  int64_t in_row0[RFRAG];
+  int a_p[RFRAG], a_q[RFRAG];
+#pragma unroll
+  for (int rf = 0; rf < RFRAG; ++rf) {
+    int arow = row0 + rf * 16 + (lane & 15);
+    if (arow >= M) arow = M - 1;
+    const int n = arow / (H * W);
+    const int rem = arow - n * (H * W);
+    a_p[rf] = rem / W;
+    a_q[rf] = rem - a_p[rf] * W;
+    in_row0[rf] = (int64_t)arow * C;  // ((n*H + p)*W + q)*C
+  }
+  const int kpart = (lane >> 4) * 8;
+  const short relu_bits = relu_in ? (short)-1 : (short)0;
+
+  f32x4 acc[RFRAG][NFRAG];
+#pragma unroll
+  for (int rf = 0; rf < RFRAG; ++rf)
+#pragma unroll
+    for (int f = 0; f < NFRAG; ++f) acc[rf][f] = {0.f, 0.f, 0.f, 0.f};
+
+  // ---- phase 1: every live A piece of the whole K range goes in flight
+  // before the first use (a load-then-use per chunk serialises one L2
+  // round trip per piece). Dead pieces keep their zeros; their address is
+  // never formed into a load.
+  s16x8 a[G::KCHUNKS][RFRAG];
+#pragma unroll
+  for (int kc = 0; kc < G::KCHUNKS; ++kc)
+#pragma unroll
+    for (int rf = 0; rf < RFRAG; ++rf) a[kc][rf] = s16x8{};
+#pragma unroll
+  for (int kc = 0; kc < G::KCHUNKS; ++kc) {
+    const int kelem = kc * 32 + kpart;
+    const int tap = kelem / C;
+    const int c0 = kelem - tap * C;
+    const int th = tap / 3;
+    const int dy = th - 1;
+    const int dx = tap - th * 3 - 1;
+    const int64_t koff = (int64_t)(dy * W + dx) * C + c0;
+#pragma unroll
+    for (int rf = 0; rf < RFRAG; ++rf) {
+      const bool live = tap < 9 && (unsigned)(a_p[rf] + dy) < (unsigned)H &&
+                        (unsigned)(a_q[rf] + dx) < (unsigned)W;
+      if (live)
+        a[kc][rf] = *reinterpret_cast<const s16x8*>(in + in_row0[rf] + koff);
+    }
+  }
+
+  // the residual goes in flight with the A pieces: 4 consecutive couts
+  // per (row-fragment, col-fragment)
+  const int ccol = (lane >> 4) * 4;
+  bf16x4 rv[RFRAG][NFRAG];
+#pragma unroll
+  for (int rf = 0; rf < RFRAG; ++rf) {
+    const int orow = row0 + rf * 16 + (lane & 15);
+#pragma unroll
+    for (int f = 0; f < NFRAG; ++f) {
+      rv[rf][f] = bf16x4{};
+      if (residual && orow < M)
+        rv[rf][f] = *reinterpret_cast<const bf16x4*>(
+            residual + (int64_t)orow * COUT + f * 16 + ccol);
+    }
+  }
+
+  // ---- phase 2: relu_in on the bf16 bits (clear every element whose sign
+  // bit is set), then the MFMAs
+#pragma unroll
+  for (int kc = 0; kc < G::KCHUNKS; ++kc) {
+    bf16x8 av[RFRAG];
+#pragma unroll
+    for (int rf = 0; rf < RFRAG; ++rf) {
+      const s16x8 s = a[kc][rf];
+      av[rf] = __builtin_bit_cast(bf16x8, s & ~((s >> 15) & relu_bits));
+    }
+#pragma unroll
+    for (int f = 0; f < NFRAG; ++f) {
+      const int col = f * 16 + (lane & 15);
+      bf16x8 b = *reinterpret_cast<const bf16x8*>(
+          wlds + col * G::LDS_ROW + kc * 32 + kpart);
+#pragma unroll
+      for (int rf = 0; rf < RFRAG; ++rf)
+        acc[rf][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, av[rf],
+                                                             acc[rf][f], 0, 0, 0);
+    }
+  }
+
+  // ---- epilogue: acc[rf][f][r] = out[row0 + rf*16 + (l&15)]
+  //                                   [f*16 + (l>>4)*4 + r]
+  // + bias, + residual, ReLU in f32; one 8-byte store per (rf, f)
+#pragma unroll
+  for (int rf = 0; rf < RFRAG; ++rf) {
+    const int orow = row0 + rf * 16 + (lane & 15);
+    if (orow >= M) continue;
+#pragma unroll
+    for (int f = 0; f < NFRAG; ++f) {
+      const bf16x4 bv = *reinterpret_cast<const bf16x4*>(blds + f * 16 + ccol);
+      bf16x4 ov;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = acc[rf][f][r] + (float)bv[r];
+        v += (float)rv[rf][f][r];
+        if (relu_out) v = v > 0.0f ? v : 0.0f;
+        ov[r] = (__bf16)v;
+      }
+      *reinterpret_cast<bf16x4*>(out + (int64_t)orow * COUT + f * 16 + ccol) =
+          ov;
+    }
+  }
+}
+
+struct Conv3Launch {
+  int H, W, C, COUT;
+  void (*fn)(const __bf16*, const __bf16*, const __bf16*, const __bf16*,
+             __bf16*, int, int, int);
+  int lds_bytes;
+  int waves, rpw;
+};
+
+template <int H, int W, int C, int COUT, int WAVES, int RPW>
+Conv3Launch make_conv3() {
+  using G = Conv3Geom<C, COUT>;
+  return Conv3Launch{H, W, C, COUT,
+                     conv3x3p1_fwd_kernel<H, W, C, COUT, WAVES, RPW>,
+                     G::LDS_BYTES, WAVES, RPW};
+}
+
+// cfg/impala_resnet.json at 84x84 (the first conv, C=4 -> K=36, stays on
+// the library)
+static const Conv3Launch kConv3Launches[] = {
+    make_conv3<42, 42, 16, 16, 8, 32>(),  // section-1 residual convs
+    make_conv3<42, 42, 16, 32, 8, 32>(),  // section-2 entry conv
+    make_conv3<21, 21, 32, 32, 8, 32>(),  // section-3 entry, sec-2 residual
+    make_conv3<11, 11, 32, 32, 8, 16>(),  // section-3 residual convs
+};
+
+const Conv3Launch* find_conv3(int64_t H, int64_t W, int64_t C, int64_t COUT) {
+  for (const auto& l : kConv3Launches)
+    if (l.H == H && l.W == W && l.C == C && l.COUT == COUT) return &l;
+  return nullptr;
+}
+
+}  // namespace
+
+bool conv3x3p1_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
+  return find_conv3(H, W, C, COUT) != nullptr;
+}
+
+// in: (N,C,H,W) logical channels_last bf16; weight: (COUT,C,3,3) logical
+// channels_last bf16; bias: (COUT) bf16 or empty; residual: same shape and
+// layout as out, or empty; out: (N,COUT,H,W) logical channels_last bf16.
+// One launch on the current stream, no allocation, no sync (graph-safe).
+void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
+                   torch::Tensor residual, torch::Tensor out, bool relu_in,
+                   bool relu_out) {
+  TORCH_CHECK(in.is_cuda() && weight.is_cuda() && out.is_cuda());
+  TORCH_CHECK(in.dim() == 4 && weight.dim() == 4 && out.dim() == 4);
+  TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv3x3p1_fwd input must be channels_last");
+  TORCH_CHECK(out.is_contiguous(at::MemoryFormat::ChannelsLast));
+  TORCH_CHECK(weight.is_contiguous(at::MemoryFormat::ChannelsLast));
+  TORCH_CHECK(in.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(weight.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16);
+  const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
+  const int64_t COUT = weight.size(0);
+  TORCH_CHECK(weight.size(1) == C && weight.size(2) == 3 && weight.size(3) == 3,
+              "conv3x3p1_fwd weight must be (COUT, C, 3, 3)");
+  TORCH_CHECK(out.size(0) == N && out.size(1) == COUT && out.size(2) == H &&
+                  out.size(3) == W,
+              "conv3x3p1_fwd output shape mismatch");
+  TORCH_CHECK(out.data_ptr() != in.data_ptr(), "conv3x3p1_fwd is not in-place");
+  // 16-byte pieces of in / weight, 8-byte pieces of out / residual
+  TORCH_CHECK((uintptr_t)in.data_ptr() % 16 == 0 &&
+                  (uintptr_t)weight.data_ptr() % 16 == 0 &&
+                  (uintptr_t)out.data_ptr() % 8 == 0,
+              "conv3x3p1_fwd: misaligned tensor");
+  const Conv3Launch* L = find_conv3(H, W, C, COUT);
+  TORCH_CHECK(L, "no 3x3 pad-1 conv kernel for this geometry: ", H, "x", W, "x",
+              C, " -> ", COUT);
+  TORCH_CHECK(N * H * W < (int64_t)1 << 31, "conv3x3p1_fwd: too many rows");
+  const __bf16* bias_ptr = nullptr;
+  if (bias.defined() && bias.numel() > 0) {
+    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == torch::kBFloat16 &&
+                bias.numel() == COUT && bias.is_contiguous());
+    bias_ptr = (const __bf16*)bias.data_ptr();
+  }
+  const __bf16* res_ptr = nullptr;
+  if (residual.defined() && residual.numel() > 0) {
+    TORCH_CHECK(residual.is_cuda() &&
+                residual.scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(residual.sizes() == out.sizes(),
+                "conv3x3p1_fwd residual must have the output's shape");
+    TORCH_CHECK(residual.is_contiguous(at::MemoryFormat::ChannelsLast));
+    TORCH_CHECK((uintptr_t)residual.data_ptr() % 8 == 0,
+                "conv3x3p1_fwd: misaligned residual");
+    res_ptr = (const __bf16*)residual.data_ptr();
+  }
+  if (N == 0) return;
+  const int M = (int)(N * H * W);
+  const int rows_per_block = L->waves * L->rpw;
+  const int blocks = (M + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), L->lds_bytes,
+                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
+                     (const __bf16*)in.data_ptr(),
+                     (const __bf16*)weight.data_ptr(), bias_ptr, res_ptr,
+                     (__bf16*)out.data_ptr(), (int)N, relu_in ? 1 : 0,
+                     relu_out ? 1 : 0);
 }

@@ -23,6 +23,22 @@ def dequant_frames(x_u8: torch.Tensor, dtype: torch.dtype = torch.float32) -> to
 
 
 # ---------------------------------------------------------------------------
+# K2b — 3x3 stride-1 pad-1 conv with the IMPALA-ResNet block fusions:
+#       relu on the input, + bias, + residual, relu on the output
+#       (models/base_agent.py ResidualBlock: x + c2(relu(c1(relu(x)))))
+# ---------------------------------------------------------------------------
+
+
+def conv3x3_res(x, weight, bias=None, relu_in: bool = False,
+                relu_out: bool = False, residual=None) -> torch.Tensor:
+    y = torch.nn.functional.conv2d(
+        torch.nn.functional.relu(x) if relu_in else x, weight, bias, padding=1)
+    if residual is not None:
+        y = y + residual
+    return torch.nn.functional.relu(y) if relu_out else y
+
+
+# ---------------------------------------------------------------------------
 # K4 — n-step double-DQN TD loss + new priority + IS-weighted loss
 #      (APE_X/Learner.py:83-114; gamma**n with done mask; TD clip to [-1,1];
 #      priority (|clip(td)|+1e-7)**alpha; loss 0.5*mean(w*td^2))
