@@ -20,6 +20,7 @@ run data-parallel across GPUs with RCCL all-reduce (parallel/ddp.py).
 
 from __future__ import annotations
 
+import os as _os
 import time
 from collections import deque
 from typing import Any, Dict, List, Optional
@@ -30,6 +31,7 @@ import torch
 from .. import ops
 from ..config import Config
 from ..models import BaseAgent
+from ..models.base_agent import CNN2D
 from ..replay import make_apex_schema, make_per
 from .common import LearnerBase
 
@@ -181,8 +183,6 @@ class ApexLearner(LearnerBase):
         )
         cnn = self.net.nodes[cnn_node]
 
-        import os as _os
-
         # own linear_relu kernel measured SLOWER than hipBLASLt at this
         # shape even after prefetch pipelining (A/B: 0.741 vs 0.576 ms
         # step) — the 49-chunk stage/sync cadence dominates; dispatch keeps
@@ -213,6 +213,15 @@ class ApexLearner(LearnerBase):
             return hidden_of(cnn(x))
 
         self._fast_hidden = fast_hidden
+        self._cnn = cnn
+        self._own_lin = own_lin
+
+        def pre_hidden_of(feat):
+            # raw (pre-ReLU) hidden for the pre-activation loss kernels
+            return F.linear(feat.to(w1.dtype), w1, b1)
+
+        self._pre_hidden_of = pre_hidden_of
+        self._hidden_of = hidden_of
         # direct-grad leaf list: the forward uses the FUSED (w1, b1) views
         # instead of the four pinned params, and w1/b1's flattened grads
         # cover exactly the flat buffer's pinned prefix
@@ -243,6 +252,10 @@ class ApexLearner(LearnerBase):
             return t_hidden_of(t_cnn(x))
 
         self._target_hidden = target_hidden
+        self._t_cnn = t_cnn
+        self._t_hidden_of = t_hidden_of
+        self._t_pre_hidden_of = (
+            lambda feat: F.linear(feat.to(w1t.dtype), w1t, b1t))
         self._thead_params = (ta_head.weight, ta_head.bias, tv_head.weight,
                               tv_head.bias)
 
@@ -494,16 +507,35 @@ class ApexLearner(LearnerBase):
         if cuda and getattr(self, "_use_q_loss", False):
             # deepest fusion: head projections + dueling + TD loss in ONE
             # kernel; backward = closed-form dh + one head-grad reduction
-            h_s = self._fast_hidden(s)
+            # DRL_PREACT_LOSS=0 / DRL_GROUPED_CONV=0 force the unfused
+            # pieces (A/B and the old-path oracle)
+            pre = (_os.environ.get("DRL_PREACT_LOSS", "1") == "1"
+                   and not self._own_lin)
+            if _os.environ.get("DRL_GROUPED_CONV", "1") == "1":
+                # one launch per conv layer for all three forwards; only
+                # the online(s) job is differentiable
+                f_s, f_on, f_tg = CNN2D.forward_grouped(
+                    [(s, self._cnn, True), (sp, self._cnn, False),
+                     (sp, self._t_cnn, False)])
+            else:
+                f_s = self._cnn(s)
+                with torch.no_grad():
+                    f_on = self._cnn(sp)
+                    f_tg = self._t_cnn(sp)
+            # pre: the FC ReLU (and its backward mask) runs inside the loss
+            # kernels, which read the same rows anyway
+            hid = self._pre_hidden_of if pre else self._hidden_of
+            t_hid = self._t_pre_hidden_of if pre else self._t_hidden_of
+            h_s = hid(f_s)
             with torch.no_grad():
-                h_on = self._fast_hidden(sp)
-                h_tg = self._target_hidden(sp)
+                h_on = hid(f_on)
+                h_tg = t_hid(f_tg)
             wa, ba, wv, bv = self._head_params
             wat, bat, wvt, bvt = self._thead_params
             loss, prio, qmean = ops.dueling_q_head_loss(
                 h_s, wa, ba, wv, bv, h_on, h_tg, wat, bat, wvt, bvt,
                 actions, rewards, dones, weights, self.gamma, self.n_step,
-                self.alpha,
+                self.alpha, pre_act=pre,
             )
         elif cuda and getattr(self, "_fast_heads", None) is not None:
             # fused whole-head path: dueling epilogues live inside the loss
@@ -537,6 +569,11 @@ class ApexLearner(LearnerBase):
     def _optimize_mp(self):
         """Upcast + optimizer + param sync (post-collective stage;
         hipGraph-capturable)."""
+        # one pass when the optimizer is the fused flat RMSprop over the
+        # single bf16 group (DRL_FUSED_OPT_TAIL=0 forces the three launches)
+        if (_os.environ.get("DRL_FUSED_OPT_TAIL", "1") == "1"
+                and self.mp.fused_step(self.optim)):
+            return
         self.mp.upcast_grads()
         self.optim.step()
         self.mp.sync_compute_params()

@@ -129,6 +129,88 @@ class CNN2D(nn.Module):
             y = torch.flatten(y, 1)
         return y
 
+    def _grouped_ok(self, x: torch.Tensor) -> bool:
+        """_fused_ok plus a grouped kernel variant for every layer."""
+        if not self._fused_ok(x):
+            return False
+        key = ("grouped", tuple(x.shape[1:]), x.dtype)
+        hit = self._fused_checked.get(key)
+        if hit is not None:
+            return hit
+        from .. import ops as _ops
+
+        ok = True
+        C, H, W = x.shape[1:]
+        u8 = x.dtype == torch.uint8
+        last = len(self._convs) - 1
+        for i, conv in enumerate(self._convs):
+            COUT, _, KH, KW = conv.weight.shape
+            S = conv.stride[0]
+            chw = (i == last and self.flatten
+                   and _ops.conv_chw_supported(H, W, C, KH, KW, S, COUT))
+            if not _ops.conv_grouped_supported(H, W, C, KH, KW, S, COUT, u8,
+                                               chw):
+                ok = False
+                break
+            H = (H - KH) // S + 1
+            W = (W - KW) // S + 1
+            C = COUT
+            u8 = False
+        self._fused_checked[key] = ok
+        return ok
+
+    @staticmethod
+    def forward_grouped(jobs) -> List[torch.Tensor]:
+        """Run several (x, module, needs_grad) jobs through their conv stacks
+        layer by layer with ONE grouped launch per layer (same results as
+        calling each module on its x). Jobs with needs_grad=False are run on
+        detached parameters, like a forward under torch.no_grad(). Falls
+        back to per-module forwards when the stacks differ, the batch sizes
+        differ, or a layer has no grouped kernel."""
+        from .. import ops as _ops
+
+        xs = [j[0] for j in jobs]
+        mods = [j[1] for j in jobs]
+        m0 = mods[0]
+        same = all(
+            m.flatten == m0.flatten and len(m._convs) == len(m0._convs)
+            and all(a.weight.shape == b.weight.shape and a.stride == b.stride
+                    and (a.bias is None) == (b.bias is None)
+                    for a, b in zip(m._convs, m0._convs))
+            for m in mods)
+        if not (same and 1 <= len(jobs) <= 4
+                and all(x.shape == xs[0].shape and x.dtype == xs[0].dtype
+                        for x in xs)
+                and all(m._grouped_ok(x) for x, m in zip(xs, mods))):
+            outs = []
+            for x, m, needs_grad in jobs:
+                with torch.set_grad_enabled(needs_grad
+                                            and torch.is_grad_enabled()):
+                    outs.append(m(x))
+            return outs
+
+        def par(t, needs_grad):
+            return t if needs_grad or t is None else t.detach()
+
+        ys = [x if g else x.detach() for x, _, g in jobs]
+        last = len(m0._convs) - 1
+        for i in range(len(m0._convs)):
+            convs = [m._convs[i] for m in mods]
+            c0 = convs[0]
+            chw = (i == last and m0.flatten and _ops.conv_chw_supported(
+                ys[0].shape[2], ys[0].shape[3], ys[0].shape[1],
+                c0.weight.shape[2], c0.weight.shape[3], c0.stride[0],
+                c0.weight.shape[0]))
+            ys = list(_ops.fused_conv_relu_grouped(
+                ys, [par(c.weight, j[2]) for c, j in zip(convs, jobs)],
+                [par(c.bias, j[2]) for c, j in zip(convs, jobs)],
+                c0.stride[0], chw_out=chw))
+            if chw:
+                return ys
+        if m0.flatten:
+            ys = [torch.flatten(y, 1) for y in ys]
+        return ys
+
 
 class MLP(nn.Module):
     def __init__(self, cfg: Dict[str, Any]):

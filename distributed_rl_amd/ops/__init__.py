@@ -127,90 +127,110 @@ class _FusedConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, weight, out = ctx.saved_tensors
-        stride = ctx.stride
-        COUT = weight.shape[0]
-        if ctx.chw:
-            # one kernel: relu-mask + CHW->NHWC transpose
-            P, Q = ctx.pq
-            N = gout.shape[0]
-            masked = torch.empty(N, COUT, P, Q, dtype=torch.bfloat16,
-                                 device=gout.device,
-                                 memory_format=torch.channels_last)
-            hip_ext().relu_mask_bwd_chw(gout.contiguous(), out, masked,
-                                        COUT, P * Q)
-            gout = masked
-        else:
-            if not gout.is_contiguous(memory_format=torch.channels_last):
-                gout = gout.contiguous(memory_format=torch.channels_last)
-            # fused ReLU mask (one kernel instead of compare+mul)
-            masked = torch.empty_like(gout)
-            hip_ext().relu_mask_bwd(gout, out, masked)
-            gout = masked
         need_x = ctx.needs_input_grad[0]
         need_w = ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        COUT, C, KH, KW = weight.shape
-        ext = hip_ext()
-        use_own_wrw = need_w and bool(
-            ext.conv_wrw_supported(x.shape[2], x.shape[3], C, KH, KW, stride,
-                                   COUT, x.dtype == torch.uint8)
-        )
-        gw = gb = None
-        if use_own_wrw:
-            # hand-written MFMA weight-grad (conv_mfma.hip): per-m-slice
-            # partials summed in a fixed order (reproducible) into the fp32
-            # workspaces, every element of which the op writes (no
-            # zero-fill); cast to the bf16 channels_last grad here
-            K = KH * KW * C
-            flat_ws = torch.empty(COUT * (K + 1), dtype=torch.float32,
-                                  device=x.device)
-            ws = flat_ws[: COUT * K].view(COUT, K)
-            gb_ws = (flat_ws[COUT * K :] if need_b
-                     else torch.empty(0, device=x.device))
-            ext.conv_wrw(x, gout, ws, gb_ws, stride)
-            gw = ws.view(COUT, KH, KW, C).permute(0, 3, 1, 2).to(torch.bfloat16)
-            if need_b:
-                gb = gb_ws.to(torch.bfloat16)
-        gi = None
-        # Hand-written dgrad exists and is oracle-tested, but MEASURED
-        # SLOWER than MIOpen's igemm at these geometries (tools/
-        # gpu_dgrad_bench.py: 133 vs 28 us at 20x20 s2, 42 vs 33 at 9x9
-        # s1) — dispatch keeps the faster library kernel; DRL_OWN_DGRAD=1
-        # forces ours (profiles/r02 notes).
-        use_own_dgrad = (
-            os.environ.get("DRL_OWN_DGRAD", "0") == "1"
-            and need_x and x.dtype == torch.bfloat16
-            and hasattr(ext, "conv_dgrad_supported")
-            and bool(ext.conv_dgrad_supported(x.shape[2], x.shape[3], C, KH,
-                                              KW, stride, COUT))
-        )
-        if use_own_dgrad:
-            # hand-written MFMA dgrad (conv_mfma.hip): masked-tap gather
-            # against a per-step transposed weight copy — no MIOpen on the
-            # hot path
-            gi = torch.empty_like(x)
-            w_t = torch.empty(weight.numel(), dtype=torch.bfloat16,
+        gi, gw, gb = _fused_conv_backward(
+            x, weight, out, gout, ctx.stride, ctx.has_bias, ctx.chw, ctx.pq,
+            need_x, need_w, need_b)
+        return gi, gw, gb, None, None
+
+
+def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
+                         need_x, need_w, need_b):
+    """Backward of one fused conv+bias+ReLU layer; returns (gi, gw, gb).
+    Shared by _FusedConvFn and _FusedConvGroupedFn."""
+    COUT = weight.shape[0]
+    if chw:
+        # one kernel: relu-mask + CHW->NHWC transpose
+        P, Q = pq
+        N = gout.shape[0]
+        masked = torch.empty(N, COUT, P, Q, dtype=torch.bfloat16,
+                             device=gout.device,
+                             memory_format=torch.channels_last)
+        hip_ext().relu_mask_bwd_chw(gout.contiguous(), out, masked,
+                                    COUT, P * Q)
+        gout = masked
+    else:
+        if not gout.is_contiguous(memory_format=torch.channels_last):
+            gout = gout.contiguous(memory_format=torch.channels_last)
+        # fused ReLU mask (one kernel instead of compare+mul)
+        masked = torch.empty_like(gout)
+        hip_ext().relu_mask_bwd(gout, out, masked)
+        gout = masked
+    COUT, C, KH, KW = weight.shape
+    ext = hip_ext()
+    use_own_wrw = need_w and bool(
+        ext.conv_wrw_supported(x.shape[2], x.shape[3], C, KH, KW, stride,
+                               COUT, x.dtype == torch.uint8)
+    )
+    gw = gb = None
+    if use_own_wrw and os.environ.get("DRL_WRW_BF16", "1") == "1":
+        # hand-written MFMA weight-grad (conv_mfma.hip): per-m-slice
+        # partials summed in a fixed order (reproducible); the ordered
+        # reduce rounds its fp32 sums and writes the bf16 grads directly.
+        # (COUT, K) in (kh, kw, c) order is the channels_last weight
+        # layout, and the op writes every element (no zero-fill)
+        gw = torch.empty(COUT, KH, KW, C, dtype=torch.bfloat16,
+                         device=x.device).permute(0, 3, 1, 2)
+        gb = (torch.empty(COUT, dtype=torch.bfloat16, device=x.device)
+              if need_b else None)
+        ext.conv_wrw(x, gout, gw,
+                     gb if need_b else torch.empty(0, device=x.device),
+                     stride)
+    elif use_own_wrw:
+        # DRL_WRW_BF16=0: fp32 workspaces + cast launches (the A/B
+        # baseline of the direct bf16 store)
+        K = KH * KW * C
+        flat_ws = torch.empty(COUT * (K + 1), dtype=torch.float32,
                               device=x.device)
-            ext.conv_dgrad(gout, weight, w_t, gi, stride)
-        if (need_x and not use_own_dgrad) or (need_w and not use_own_wrw):
-            if x.dtype == torch.uint8:
-                # NHWC u8 -> bf16 for the aten path (own wrw reads u8 directly)
-                xf = dequant_frames(x.permute(0, 2, 3, 1), torch.bfloat16)
-                xf = xf.permute(0, 3, 1, 2)
-            else:
-                xf = x
-            gi2, gw2, gb2 = torch.ops.aten.convolution_backward(
-                gout, xf, weight,
-                [COUT] if ctx.has_bias else None,
-                [stride, stride], [0, 0], [1, 1], False, [0, 0], 1,
-                [need_x and not use_own_dgrad, need_w and not use_own_wrw,
-                 need_b and not use_own_wrw],
-            )
-            if gi is None:
-                gi = gi2
-            if gw is None:
-                gw, gb = gw2, gb2
-        return (gi if need_x else None), gw, gb, None, None
+        ws = flat_ws[: COUT * K].view(COUT, K)
+        gb_ws = (flat_ws[COUT * K :] if need_b
+                 else torch.empty(0, device=x.device))
+        ext.conv_wrw(x, gout, ws, gb_ws, stride)
+        gw = ws.view(COUT, KH, KW, C).permute(0, 3, 1, 2).to(torch.bfloat16)
+        if need_b:
+            gb = gb_ws.to(torch.bfloat16)
+    gi = None
+    # Hand-written dgrad exists and is oracle-tested, but MEASURED
+    # SLOWER than MIOpen's igemm at these geometries (tools/
+    # gpu_dgrad_bench.py: 133 vs 28 us at 20x20 s2, 42 vs 33 at 9x9
+    # s1) — dispatch keeps the faster library kernel; DRL_OWN_DGRAD=1
+    # forces ours (profiles/r02 notes).
+    use_own_dgrad = (
+        os.environ.get("DRL_OWN_DGRAD", "0") == "1"
+        and need_x and x.dtype == torch.bfloat16
+        and hasattr(ext, "conv_dgrad_supported")
+        and bool(ext.conv_dgrad_supported(x.shape[2], x.shape[3], C, KH,
+                                          KW, stride, COUT))
+    )
+    if use_own_dgrad:
+        # hand-written MFMA dgrad (conv_mfma.hip): masked-tap gather
+        # against a per-step transposed weight copy — no MIOpen on the
+        # hot path
+        gi = torch.empty_like(x)
+        w_t = torch.empty(weight.numel(), dtype=torch.bfloat16,
+                          device=x.device)
+        ext.conv_dgrad(gout, weight, w_t, gi, stride)
+    if (need_x and not use_own_dgrad) or (need_w and not use_own_wrw):
+        if x.dtype == torch.uint8:
+            # NHWC u8 -> bf16 for the aten path (own wrw reads u8 directly)
+            xf = dequant_frames(x.permute(0, 2, 3, 1), torch.bfloat16)
+            xf = xf.permute(0, 3, 1, 2)
+        else:
+            xf = x
+        gi2, gw2, gb2 = torch.ops.aten.convolution_backward(
+            gout, xf, weight,
+            [COUT] if has_bias else None,
+            [stride, stride], [0, 0], [1, 1], False, [0, 0], 1,
+            [need_x and not use_own_dgrad, need_w and not use_own_wrw,
+             need_b and not use_own_wrw],
+        )
+        if gi is None:
+            gi = gi2
+        if gw is None:
+            gw, gb = gw2, gb2
+    return (gi if need_x else None), gw, gb
 
 
 def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
@@ -218,6 +238,99 @@ def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
     chw_out=True additionally fuses the trailing flatten into the epilogue
     (returns 2-D (N, COUT*P*Q) in logical-NCHW order)."""
     return _FusedConvFn.apply(x, weight, bias, stride, chw_out)
+
+
+def conv_grouped_supported(H, W, C, KH, KW, S, COUT, u8: bool,
+                           chw_out: bool = False) -> bool:
+    ext = hip_ext(required=False)
+    return ext is not None and hasattr(ext, "conv_fwd_grouped_supported") and \
+        bool(ext.conv_fwd_grouped_supported(H, W, C, KH, KW, S, COUT, u8,
+                                            chw_out))
+
+
+class _FusedConvGroupedFn(torch.autograd.Function):
+    """Several independent same-geometry conv+bias+ReLU layers (e.g. the
+    online(s), online(s'), target(s') forwards of one Ape-X step) in ONE
+    launch. args = xs + weights + biases (biases all None or all tensors).
+    The backward runs the single-job backward for the jobs whose inputs or
+    parameters require grad; the other jobs' outputs are non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, stride, chw_out, njobs, *args):
+        ext = hip_ext()
+        xs = list(args[:njobs])
+        ws = list(args[njobs : 2 * njobs])
+        bs = list(args[2 * njobs :])
+        has_bias = bs[0] is not None
+        assert all((b is not None) == has_bias for b in bs), \
+            "grouped conv: biases must be all set or all None"
+        x0, w0 = xs[0], ws[0]
+        N, C, H, W = x0.shape
+        COUT, _, KH, KW = w0.shape
+        P = (H - KH) // stride + 1
+        Q = (W - KW) // stride + 1
+        if chw_out:
+            outs = [torch.empty(N, COUT * P * Q, dtype=torch.bfloat16,
+                                device=x0.device) for _ in range(njobs)]
+        else:
+            outs = [torch.empty(N, COUT, P, Q, dtype=torch.bfloat16,
+                                device=x0.device,
+                                memory_format=torch.channels_last)
+                    for _ in range(njobs)]
+        ext.conv_fwd_grouped(xs, ws, bs if has_bias else [], outs, stride,
+                             chw_out)
+        live = [any(ctx.needs_input_grad[3 + k * njobs + j] for k in range(3))
+                for j in range(njobs)]
+        saved = []
+        for j in range(njobs):
+            if live[j]:
+                saved += [xs[j], ws[j], outs[j]]
+        ctx.save_for_backward(*saved)
+        dead = [outs[j] for j in range(njobs) if not live[j]]
+        if dead:
+            ctx.mark_non_differentiable(*dead)
+        ctx.live = live
+        ctx.njobs = njobs
+        ctx.stride = stride
+        ctx.has_bias = has_bias
+        ctx.chw = chw_out
+        ctx.pq = (P, Q)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        n = ctx.njobs
+        grads = [None] * (3 * n)
+        saved = ctx.saved_tensors
+        k = 0
+        for j in range(n):
+            if not ctx.live[j]:
+                continue
+            x, weight, out = saved[k : k + 3]
+            k += 3
+            if gouts[j] is None:
+                continue
+            need_x = ctx.needs_input_grad[3 + j]
+            need_w = ctx.needs_input_grad[3 + n + j]
+            need_b = ctx.has_bias and ctx.needs_input_grad[3 + 2 * n + j]
+            gi, gw, gb = _fused_conv_backward(
+                x, weight, out, gouts[j], ctx.stride, ctx.has_bias, ctx.chw,
+                ctx.pq, need_x, need_w, need_b)
+            grads[j], grads[n + j], grads[2 * n + j] = gi, gw, gb
+        return (None, None, None, *grads)
+
+
+def fused_conv_relu_grouped(xs, weights, biases, stride: int,
+                            chw_out: bool = False):
+    """fused_conv_relu for several (x, weight, bias) jobs of one geometry and
+    batch size in a single launch; returns one output per job, each
+    bit-identical to its own fused_conv_relu call. Pass detached parameters
+    for jobs that must not receive gradients."""
+    n = len(xs)
+    assert len(weights) == n and len(biases) == n
+    return _FusedConvGroupedFn.apply(stride, bool(chw_out), n, *xs, *weights,
+                                     *biases)
 
 
 # ---------------------------------------------------------------------------
@@ -532,7 +645,8 @@ def has_dueling_q_loss(hidden: int, actions: int) -> bool:
 class _DuelingQLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h_s, wa, ba, wv, bv, h_on, h_tg, wa_t, ba_t, wv_t, bv_t,
-                actions, rewards, dones, weights, gamma_n, alpha):
+                actions, rewards, dones, weights, gamma_n, alpha,
+                pre_act=False):
         ext = hip_ext()
         B = h_s.shape[0]
         dev = h_s.device
@@ -546,8 +660,9 @@ class _DuelingQLossFn(torch.autograd.Function):
             wv_t.reshape(-1).contiguous(), bv_t.contiguous(),
             actions.contiguous(), rewards.contiguous(), dones.contiguous(),
             weights.contiguous(), float(gamma_n), float(alpha),
-            acc2[0:1], prio, coef, acc2[1:2],
+            acc2[0:1], prio, coef, acc2[1:2], bool(pre_act),
         )
+        ctx.pre_act = bool(pre_act)
         ctx.save_for_backward(coef, actions, wa, wv, h_s)
         loss_out, qmean = acc2[0], acc2[1]
         ctx.mark_non_differentiable(prio, qmean)
@@ -566,8 +681,9 @@ class _DuelingQLossFn(torch.autograd.Function):
         dbv = torch.empty(1, dtype=torch.bfloat16, device=dev)
         ext.dueling_q_loss_bwd(coef, actions, gout.reshape(1).contiguous(),
                                wa.contiguous(), wv.reshape(-1).contiguous(),
-                               h_s.contiguous(), dh, dwa, dba, dwv, dbv)
-        return (dh, dwa, dba, dwv, dbv) + (None,) * 12
+                               h_s.contiguous(), dh, dwa, dba, dwv, dbv,
+                               ctx.pre_act)
+        return (dh, dwa, dba, dwv, dbv) + (None,) * 13
 
 
 def has_r2d2_seq_loss() -> bool:
@@ -627,17 +743,22 @@ def r2d2_sequence_loss(q_train, q_tgt, actions, rewards, done, weights,
 
 def dueling_q_head_loss(h_s, wa, ba, wv, bv, h_on, h_tg, wa_t, ba_t, wv_t,
                         bv_t, actions, rewards, dones, weights, gamma: float,
-                        n_step: int, alpha: float):
+                        n_step: int, alpha: float, pre_act: bool = False):
     """Heads + dueling + n-step double-DQN loss fully fused.
-    h_*: (B, 1024) = [adv-stream | val-stream] post-ReLU hidden.
+    h_*: (B, 1024) = [adv-stream | val-stream] post-ReLU hidden, or with
+    pre_act=True the raw pre-activation output of the hidden layer (the
+    kernels then apply the ReLU and its backward mask themselves).
     Only (h_s, wa, ba, wv, bv) are differentiable."""
     if _use_hip(h_s):
         return _DuelingQLossFn.apply(
             h_s, wa, ba, wv, bv, h_on, h_tg, wa_t, ba_t, wv_t, bv_t,
             actions.long(), rewards.float(), dones.float(), weights.float(),
-            gamma ** n_step, alpha,
+            gamma ** n_step, alpha, pre_act,
         )
     import torch.nn.functional as F
+
+    if pre_act:
+        h_s, h_on, h_tg = F.relu(h_s), F.relu(h_on), F.relu(h_tg)
 
     def heads(h, wa_, ba_, wv_, bv_):
         return (F.linear(h[:, :512].float(), wa_.float(), ba_.float()),

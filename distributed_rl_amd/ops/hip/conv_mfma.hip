@@ -56,15 +56,13 @@ struct ConvGeom {
 // 8.6 us x 3 forwards per Ape-X step).
 template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8IN,
           int WAVES, int RPW, bool CHW_OUT = false>
-__global__ __launch_bounds__(WAVES * 64) void conv_fwd_kernel(
+__device__ __forceinline__ void conv_fwd_block(
     const void* __restrict__ in_v,       // (N,H,W,C) u8 or bf16 (NHWC)
     const __bf16* __restrict__ weight,   // (COUT, K) row-major NHWC flat
     const __bf16* __restrict__ bias,     // (COUT), may be null
     __bf16* __restrict__ out,            // (N,P,Q,COUT)
-    int batch) {
+    int batch, int tile, __bf16* wlds) {
   using G = ConvGeom<H, W, C, KH, KW, S, COUT, U8IN>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* wlds = reinterpret_cast<__bf16*>(smem);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_fwd_kernel(
   __syncthreads();
 
   const int M = batch * G::P * G::Q;
-  const int row0 = (blockIdx.x * WAVES + wave) * RPW;
+  const int row0 = (tile * WAVES + wave) * RPW;
   if (row0 >= M) return;
   constexpr int RFRAG = RPW / 16;
   constexpr int NFRAG = COUT / 16;
@@ -168,37 +166,83 @@ __global__ __launch_bounds__(WAVES * 64) void conv_fwd_kernel(
     }
 }
 
+template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8IN,
+          int WAVES, int RPW, bool CHW_OUT = false>
+__global__ __launch_bounds__(WAVES * 64) void conv_fwd_kernel(
+    const void* __restrict__ in_v, const __bf16* __restrict__ weight,
+    const __bf16* __restrict__ bias, __bf16* __restrict__ out, int batch) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  conv_fwd_block<H, W, C, KH, KW, S, COUT, U8IN, WAVES, RPW, CHW_OUT>(
+      in_v, weight, bias, out, batch, blockIdx.x,
+      reinterpret_cast<__bf16*>(smem));
+}
+
+// Grouped forward: up to kMaxConvJobs independent {in, weight, bias, out}
+// jobs of ONE geometry and batch size in a single launch. The job table
+// travels by value in the kernel arguments (no device-side pointer table:
+// nothing to upload, graph-replay safe). Block numbering is job-minor —
+// block b runs row tile b / njobs of job b % njobs — so the blocks of
+// different jobs on the same row tile are adjacent in dispatch order and
+// jobs that share an input re-read it from L2. Each block runs the
+// single-job body unchanged, so a job's output is bit-identical to its own
+// conv_fwd launch.
+constexpr int kMaxConvJobs = 4;
+struct ConvJobs {
+  const void* in[kMaxConvJobs];
+  const __bf16* weight[kMaxConvJobs];
+  const __bf16* bias[kMaxConvJobs];
+  __bf16* out[kMaxConvJobs];
+};
+
+template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8IN,
+          int WAVES, int RPW, bool CHW_OUT = false>
+__global__ __launch_bounds__(WAVES * 64) void conv_fwd_grouped_kernel(
+    const ConvJobs jobs, int njobs, int batch) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tile = blockIdx.x / njobs;
+  const int job = blockIdx.x - tile * njobs;
+  conv_fwd_block<H, W, C, KH, KW, S, COUT, U8IN, WAVES, RPW, CHW_OUT>(
+      jobs.in[job], jobs.weight[job], jobs.bias[job], jobs.out[job], batch,
+      tile, reinterpret_cast<__bf16*>(smem));
+}
+
 struct ConvLaunch {
   int H, W, C, KH, KW, S, COUT;
   bool u8;
   void (*fn)(const void*, const __bf16*, const __bf16*, __bf16*, int);
   int lds_bytes;
   int waves, rpw;
+  void (*grouped)(const ConvJobs, int, int);  // null: no grouped variant
 };
 
 template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8,
-          int WAVES = 4, int RPW = 16, bool CHW = false>
+          int WAVES = 4, int RPW = 16, bool CHW = false, bool GROUPED = false>
 ConvLaunch make_launch() {
   using G = ConvGeom<H, W, C, KH, KW, S, COUT, U8>;
+  void (*grouped)(const ConvJobs, int, int) = nullptr;
+  if constexpr (GROUPED)
+    grouped = conv_fwd_grouped_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW,
+                                      CHW>;
   return ConvLaunch{H, W, C, KH, KW, S, COUT, U8,
                     conv_fwd_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW,
                                     CHW>,
-                    (int)(G::LDS_ELEMS * sizeof(__bf16)), WAVES, RPW};
+                    (int)(G::LDS_ELEMS * sizeof(__bf16)), WAVES, RPW, grouped};
 }
 
 // CHW-out variants for the stack-final conv of each model (flatten fusion)
 static const ConvLaunch kChwLaunches[] = {
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16, true>(),
+    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16, true, true>(),
     make_launch<20, 20, 16, 4, 4, 2, 32, false, 8, 16, true>(),
 };
 
 static const ConvLaunch kLaunches[] = {
     // Ape-X / R2D2 stack (cfg/ape_x.json:38-51); WAVES/RPW picked by the
     // variant sweep in tools/gpu_conv_tune.py (profiles/)
-    make_launch<84, 84, 4, 8, 8, 4, 32, true, 8, 32>(),
-    make_launch<84, 84, 4, 8, 8, 4, 32, false, 8, 32>(),
-    make_launch<20, 20, 32, 4, 4, 2, 64, false, 8, 16>(),
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16>(),
+    // (these four also carry the grouped variant)
+    make_launch<84, 84, 4, 8, 8, 4, 32, true, 8, 32, false, true>(),
+    make_launch<84, 84, 4, 8, 8, 4, 32, false, 8, 32, false, true>(),
+    make_launch<20, 20, 32, 4, 4, 2, 64, false, 8, 16, false, true>(),
+    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16, false, true>(),
     // IMPALA stack (cfg/impala.json:26-39)
     make_launch<84, 84, 4, 8, 8, 4, 16, true, 8, 16>(),
     make_launch<84, 84, 4, 8, 8, 4, 16, false, 8, 16>(),
@@ -350,6 +394,14 @@ bool conv_fwd_chw_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
                             int64_t KW, int64_t S, int64_t COUT);
 void relu_mask_bwd_chw(torch::Tensor gout2d, torch::Tensor out2d,
                        torch::Tensor dst_nhwc, int64_t C, int64_t PQ);
+void conv_fwd_grouped(std::vector<torch::Tensor> ins,
+                      std::vector<torch::Tensor> weights,
+                      std::vector<torch::Tensor> biases,
+                      std::vector<torch::Tensor> outs, int64_t stride,
+                      bool chw_out);  // defined below
+bool conv_fwd_grouped_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
+                                int64_t KW, int64_t S, int64_t COUT, bool u8,
+                                bool chw_out);
 void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                  torch::Tensor out);  // defined below
 bool linear_relu_supported(int64_t K, int64_t N);
@@ -365,7 +417,11 @@ void register_conv(pybind11::module_& m) {
   m.def("conv_fwd_supported", &conv_fwd_supported);
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA fragment-map probe");
   m.def("conv_fwd_variant", &conv_fwd_variant, "tuning-variant conv fwd");
-  m.def("conv_wrw", &conv_wrw, "MFMA conv weight-grad (fp32 workspace)");
+  m.def("conv_fwd_grouped", &conv_fwd_grouped,
+        "conv_fwd / conv_fwd_chw for up to 4 same-geometry jobs in one launch");
+  m.def("conv_fwd_grouped_supported", &conv_fwd_grouped_supported);
+  m.def("conv_wrw", &conv_wrw,
+        "MFMA conv weight-grad; gw/gb are fp32 workspaces or bf16 grads");
   m.def("conv_wrw_supported", &conv_wrw_supported);
   m.def("conv_dgrad", &conv_dgrad,
         "MFMA conv data-grad (masked-tap gather, pre-transposed weights)");
@@ -553,10 +609,15 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(
 // float4) x 16 plane groups; group g adds planes g, g+16, ... in order, then
 // the group sums fold in group order. The last block (bias == true launches one
 // extra) folds the bias-grad partials of colsum_bf16_kernel the same way.
+// OutT = float writes the fp32 workspaces; OutT = __bf16 rounds the final
+// fp32 sums (round-to-nearest-even, what Tensor.to(bfloat16) does) and
+// writes the bf16 gradients directly — (COUT, K) in (kh, kw, c) order IS the
+// channels_last weight layout, so no cast or relayout pass follows.
+template <typename OutT>
 __global__ __launch_bounds__(256) void wrw_reduce_kernel(
     const float* __restrict__ part, int planes, int n_elem,
-    float* __restrict__ out, const float* __restrict__ b_part, int b_planes,
-    int cout, float* __restrict__ b_out) {
+    OutT* __restrict__ out, const float* __restrict__ b_part, int b_planes,
+    int cout, OutT* __restrict__ b_out) {
   __shared__ __attribute__((aligned(16))) float sh4_raw[256 * 4];
   float* sh = sh4_raw;
   const int tid = threadIdx.x;
@@ -592,7 +653,12 @@ __global__ __launch_bounds__(256) void wrw_reduce_kernel(
         const float4 v = sh4[k * 16 + tid];
         t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
       }
-      *reinterpret_cast<float4*>(out + e4) = t;
+      if constexpr (std::is_same<OutT, float>::value) {
+        *reinterpret_cast<float4*>(out + e4) = t;
+      } else {
+        v4bf_w o = {(__bf16)t.x, (__bf16)t.y, (__bf16)t.z, (__bf16)t.w};
+        *reinterpret_cast<v4bf_w*>(out + e4) = o;
+      }
     }
   } else {
     // bias fold: thread (g, c) adds block partials g, g+G, ...; G = 256/cout
@@ -605,7 +671,7 @@ __global__ __launch_bounds__(256) void wrw_reduce_kernel(
     if (tid < cout) {
       float t = 0.0f;
       for (int k = 0; k < G; ++k) t += sh[k * cout + tid];
-      b_out[tid] = t;
+      b_out[tid] = (OutT)t;
     }
   }
 }
@@ -689,12 +755,18 @@ bool conv_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
 
 // in: (N,C,H,W) channels_last u8/bf16; gout: (N,COUT,P,Q) channels_last bf16
 // (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 and gb_ws: (COUT) fp32
-// (or empty), both fully overwritten.
+// (or empty), both fully overwritten. bf16 gw_ws/gb_ws are the gradients
+// themselves: gw_ws then holds COUT*KH*KW*C elements in (cout, kh, kw, c)
+// memory order (a channels_last weight-shaped tensor or its flat view).
 void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
               torch::Tensor gb_ws, int64_t stride) {
   TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast));
   TORCH_CHECK(gout.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(gw_ws.scalar_type() == torch::kFloat32 && gw_ws.is_contiguous());
+  const bool bf16_out = gw_ws.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf16_out || gw_ws.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(gw_ws.is_contiguous() ||
+              (gw_ws.dim() == 4 &&
+               gw_ws.is_contiguous(at::MemoryFormat::ChannelsLast)));
   const int N = (int)in.size(0), C = (int)in.size(1), H = (int)in.size(2),
             W = (int)in.size(3);
   const int COUT = (int)gout.size(1);
@@ -725,8 +797,8 @@ void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
   TORCH_CHECK(n_elem == COUT * L->ktiles * 64, "gw_ws shape mismatch");
   // per-m-slice partial planes (every (ktile, m-slice) block writes its
   // whole 64 x COUT tile, so no zero-fill) + ordered reduction
-  auto part = torch::empty({(int64_t)mb, (int64_t)n_elem + kPlanePad},
-                           gw_ws.options());
+  const auto f32 = gw_ws.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)mb, (int64_t)n_elem + kPlanePad}, f32);
   hipLaunchKernelGGL(L->fn, dim3(L->ktiles, mb), dim3(256), L->lds_bytes, st,
                      (const void*)in.data_ptr(), (const __bf16*)gout.data_ptr(),
                      part.data_ptr<float>(), N, mb);
@@ -734,9 +806,9 @@ void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
   constexpr int kColsumBlocks = 256;
   torch::Tensor b_part;
   if (bias) {
-    TORCH_CHECK(gb_ws.numel() == COUT && gb_ws.scalar_type() == torch::kFloat32);
-    b_part = torch::empty({(int64_t)kColsumBlocks, (int64_t)COUT},
-                          gw_ws.options());
+    TORCH_CHECK(gb_ws.numel() == COUT && gb_ws.is_contiguous() &&
+                gb_ws.scalar_type() == gw_ws.scalar_type());
+    b_part = torch::empty({(int64_t)kColsumBlocks, (int64_t)COUT}, f32);
     const int64_t Mrows = (int64_t)N * P * Q;
     switch (COUT) {
       case 16:
@@ -759,11 +831,20 @@ void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
     }
   }
   const int e_blocks = (n_elem + 63) / 64;
-  hipLaunchKernelGGL(wrw_reduce_kernel, dim3(e_blocks + (bias ? 1 : 0)),
-                     dim3(256), 0, st, (const float*)part.data_ptr<float>(), mb,
-                     n_elem, gw_ws.data_ptr<float>(),
-                     bias ? (const float*)b_part.data_ptr<float>() : nullptr,
-                     kColsumBlocks, COUT, bias ? gb_ws.data_ptr<float>() : nullptr);
+  const float* b_part_ptr =
+      bias ? (const float*)b_part.data_ptr<float>() : nullptr;
+  if (bf16_out)
+    hipLaunchKernelGGL(wrw_reduce_kernel<__bf16>,
+                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), mb, n_elem,
+                       (__bf16*)gw_ws.data_ptr(), b_part_ptr, kColsumBlocks,
+                       COUT, bias ? (__bf16*)gb_ws.data_ptr() : nullptr);
+  else
+    hipLaunchKernelGGL(wrw_reduce_kernel<float>,
+                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), mb, n_elem,
+                       gw_ws.data_ptr<float>(), b_part_ptr, kColsumBlocks, COUT,
+                       bias ? gb_ws.data_ptr<float>() : nullptr);
 }
 
 // tr16 semantics probe: fill LDS with 0..511, each lane passes base +
@@ -1013,6 +1094,102 @@ void conv_fwd_chw(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
                      (const void*)in.data_ptr(),
                      (const __bf16*)weight.data_ptr(), bias_ptr,
                      (__bf16*)out2d.data_ptr(), N);
+}
+
+// Grouped conv_fwd / conv_fwd_chw: one launch for up to kMaxConvJobs jobs of
+// the same geometry and batch size (see conv_fwd_grouped_kernel). biases is
+// either empty (no job has a bias) or one tensor per job.
+void conv_fwd_grouped(std::vector<torch::Tensor> ins,
+                      std::vector<torch::Tensor> weights,
+                      std::vector<torch::Tensor> biases,
+                      std::vector<torch::Tensor> outs, int64_t stride,
+                      bool chw_out) {
+  const int njobs = (int)ins.size();
+  TORCH_CHECK(njobs >= 1 && njobs <= kMaxConvJobs, "1..", kMaxConvJobs,
+              " conv jobs per grouped launch");
+  TORCH_CHECK((int)weights.size() == njobs && (int)outs.size() == njobs &&
+              (biases.empty() || (int)biases.size() == njobs));
+  const auto& in0 = ins[0];
+  const auto& w0 = weights[0];
+  const int N = (int)in0.size(0), C = (int)in0.size(1), H = (int)in0.size(2),
+            W = (int)in0.size(3);
+  const int COUT = (int)w0.size(0), KH = (int)w0.size(2), KW = (int)w0.size(3);
+  const bool u8 = in0.scalar_type() == torch::kUInt8;
+  const int P = (H - KH) / (int)stride + 1, Q = (W - KW) / (int)stride + 1;
+  ConvJobs jobs{};
+  for (int j = 0; j < njobs; ++j) {
+    const auto& in = ins[j];
+    const auto& w = weights[j];
+    const auto& out = outs[j];
+    TORCH_CHECK(in.is_cuda() && w.is_cuda() && out.is_cuda());
+    TORCH_CHECK(in.dim() == 4 && in.sizes() == in0.sizes() &&
+                    in.scalar_type() == in0.scalar_type(),
+                "grouped conv jobs must share N and input geometry");
+    TORCH_CHECK(u8 || in.scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(w.dim() == 4 && w.sizes() == w0.sizes() && w.size(1) == C &&
+                    w.scalar_type() == torch::kBFloat16,
+                "grouped conv jobs must share the weight geometry");
+    TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv_fwd_grouped input must be channels_last");
+    TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast));
+    TORCH_CHECK(out.scalar_type() == torch::kBFloat16 &&
+                out.numel() == (int64_t)N * COUT * P * Q);
+    if (chw_out) {
+      TORCH_CHECK(out.dim() == 2 && out.is_contiguous());
+    } else {
+      TORCH_CHECK(out.dim() == 4 && out.size(0) == N && out.size(1) == COUT &&
+                  out.size(2) == P && out.size(3) == Q &&
+                  out.is_contiguous(at::MemoryFormat::ChannelsLast));
+    }
+    jobs.in[j] = in.data_ptr();
+    jobs.weight[j] = (const __bf16*)w.data_ptr();
+    jobs.out[j] = (__bf16*)out.data_ptr();
+    jobs.bias[j] = nullptr;
+    if (!biases.empty() && biases[j].defined() && biases[j].numel() > 0) {
+      TORCH_CHECK(biases[j].scalar_type() == torch::kBFloat16 &&
+                  biases[j].numel() == COUT && biases[j].is_cuda());
+      jobs.bias[j] = (const __bf16*)biases[j].data_ptr();
+    }
+  }
+  const ConvLaunch* L = nullptr;
+  auto match = [&](const ConvLaunch& l) {
+    return l.grouped && l.H == H && l.W == W && l.C == C && l.KH == KH &&
+           l.KW == KW && l.S == (int)stride && l.COUT == COUT && l.u8 == u8;
+  };
+  if (chw_out) {
+    for (const auto& l : kChwLaunches)
+      if (match(l)) { L = &l; break; }
+  } else {
+    for (const auto& l : kLaunches)
+      if (match(l)) { L = &l; break; }
+  }
+  TORCH_CHECK(L, "no grouped conv kernel for this geometry: ", H, "x", W, "x",
+              C, " k", KH, "x", KW, " s", stride, " -> ", COUT, " u8=", u8,
+              " chw=", chw_out);
+  const int M = N * P * Q;
+  const int rows_per_block = L->waves * L->rpw;
+  const int tiles = (M + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(L->grouped, dim3(tiles * njobs), dim3(L->waves * 64),
+                     L->lds_bytes,
+                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
+                     jobs, njobs, N);
+}
+
+bool conv_fwd_grouped_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
+                                int64_t KW, int64_t S, int64_t COUT, bool u8,
+                                bool chw_out) {
+  auto match = [&](const ConvLaunch& l) {
+    return l.grouped && l.H == H && l.W == W && l.C == C && l.KH == KH &&
+           l.KW == KW && l.S == S && l.COUT == COUT && l.u8 == u8;
+  };
+  if (chw_out) {
+    for (const auto& l : kChwLaunches)
+      if (match(l)) return true;
+  } else {
+    for (const auto& l : kLaunches)
+      if (match(l)) return true;
+  }
+  return false;
 }
 
 // relu-mask + CHW->NHWC transpose in one pass (backward of the fused

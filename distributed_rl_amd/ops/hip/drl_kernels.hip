@@ -712,7 +712,9 @@ void impala_out_bwd(torch::Tensor pi_save, torch::Tensor H_save,
                     int64_t T, int64_t A, double er, torch::Tensor dout);
 void rmsprop_step(torch::Tensor p, torch::Tensor g, torch::Tensor sq,
                   torch::Tensor ga, torch::Tensor mom, double lr, double alpha,
-                  double eps, double wd, double mu, bool centered, bool has_mom);
+                  double eps, double wd, double mu, bool centered, bool has_mom,
+                  c10::optional<torch::Tensor> g_bf16, double grad_scale,
+                  c10::optional<torch::Tensor> p_bf16);
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                torch::Tensor v, torch::Tensor step, double lr, double b1,
                double b2, double eps, double wd);
@@ -766,12 +768,12 @@ void dueling_q_loss_fwd(torch::Tensor h_s, torch::Tensor h_on,
                         torch::Tensor rew, torch::Tensor done, torch::Tensor w,
                         double gamma_n, double alpha, torch::Tensor loss_out,
                         torch::Tensor prio_out, torch::Tensor grad_coef,
-                        torch::Tensor qmax_out);
+                        torch::Tensor qmax_out, bool pre_act);
 void dueling_q_loss_bwd(torch::Tensor grad_coef, torch::Tensor act,
                         torch::Tensor gout, torch::Tensor wa, torch::Tensor wv,
                         torch::Tensor h_s, torch::Tensor dh, torch::Tensor dwa,
                         torch::Tensor dba, torch::Tensor dwv,
-                        torch::Tensor dbv);
+                        torch::Tensor dbv, bool pre_act);
 void r2d2_loss_fwd(torch::Tensor q_train, torch::Tensor q_tgt,
                    torch::Tensor act, torch::Tensor rew, torch::Tensor done,
                    torch::Tensor w, int64_t m, int64_t n_step, double gamma,
@@ -815,7 +817,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused IMPALA total loss: pg objective + entropy + critic MSE (K9)");
   m.def("impala_out_bwd", &impala_out_bwd,
         "IMPALA whole-head backward: d loss/d out in one launch (K9)");
-  m.def("rmsprop_step", &rmsprop_step, "fused flat centered RMSprop (K12)");
+  m.def("rmsprop_step", &rmsprop_step,
+        "fused flat centered RMSprop (K12); optional bf16 grad source "
+        "(* grad_scale) and bf16 param shadow fold the mixed-precision "
+        "upcast and param sync into the same pass",
+        pybind11::arg("p"), pybind11::arg("g"), pybind11::arg("sq"),
+        pybind11::arg("ga"), pybind11::arg("mom"), pybind11::arg("lr"),
+        pybind11::arg("alpha"), pybind11::arg("eps"), pybind11::arg("wd"),
+        pybind11::arg("mu"), pybind11::arg("centered"),
+        pybind11::arg("has_mom"), pybind11::arg("g_bf16") = pybind11::none(),
+        pybind11::arg("grad_scale") = 1.0,
+        pybind11::arg("p_bf16") = pybind11::none());
   m.def("adam_step", &adam_step, "fused flat Adam (K12)");
   m.def("lstm_step_fused", &lstm_step_fused,
         "one-kernel LSTM timestep: fp32-MFMA hh GEMM + cell (K5)");
@@ -1241,16 +1253,37 @@ void impala_out_bwd(torch::Tensor pi_save, torch::Tensor H_save,
 // foreach RMSprop costs ~170 us/step for a 1.7M-param model (6 x
 // multi_tensor_apply passes, profiles/); the whole centered-RMSprop update
 // is one memory-bound pass here. Math matches torch.optim exactly.
+// FUSED_TAIL folds the mixed-precision plumbing around the step into the
+// same pass: the gradient is read from the bf16 compute-grad buffer
+// (upcast, then * grad_scale when SCALE — the 1/world of the data-parallel
+// mean, a separately rounded fp32 multiply like the standalone upcast) and
+// the updated master is also written to the bf16 compute-param shadow.
 namespace {
+template <bool FUSED_TAIL, bool SCALE>
 __global__ void rmsprop_step_kernel(
     float* __restrict__ p, const float* __restrict__ g,
     float* __restrict__ sq, float* __restrict__ ga, float* __restrict__ mom,
     int64_t n, float lr, float alpha, float eps, float wd, float mu,
-    bool centered, bool has_mom) {
+    bool centered, bool has_mom, const __bf16* __restrict__ g_bf16,
+    float grad_scale, __bf16* __restrict__ p_bf16) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    float grad = g[i] + wd * p[i];
+    float gi;
+    if constexpr (FUSED_TAIL) {
+      gi = (float)g_bf16[i];
+      if constexpr (SCALE) {
+        // the standalone upcast rounds g * scale before the optimizer sees
+        // it; the empty asm keeps the compiler from contracting this
+        // multiply into the weight-decay add below (which would instead
+        // round wd * p separately)
+        gi = gi * grad_scale;
+        asm volatile("" : "+v"(gi));
+      }
+    } else {
+      gi = g[i];
+    }
+    float grad = gi + wd * p[i];
     float s = alpha * sq[i] + (1.0f - alpha) * grad * grad;
     sq[i] = s;
     float avg;
@@ -1267,7 +1300,9 @@ __global__ void rmsprop_step_kernel(
       mom[i] = m;
       upd = m;
     }
-    p[i] -= lr * upd;
+    const float pn = p[i] - lr * upd;
+    p[i] = pn;
+    if constexpr (FUSED_TAIL) p_bf16[i] = (__bf16)pn;
   }
 }
 
@@ -1299,15 +1334,48 @@ __global__ void adam_step_kernel(
 void rmsprop_step(torch::Tensor p, torch::Tensor g, torch::Tensor sq,
                   torch::Tensor ga, torch::Tensor mom, double lr, double alpha,
                   double eps, double wd, double mu, bool centered,
-                  bool has_mom) {
+                  bool has_mom, c10::optional<torch::Tensor> g_bf16,
+                  double grad_scale, c10::optional<torch::Tensor> p_bf16) {
   int64_t n = p.numel();
-  hipLaunchKernelGGL(rmsprop_step_kernel, dim3(grid_for(n, 4)), dim3(kBlock), 0,
-                     cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(),
-                     sq.data_ptr<float>(),
-                     centered ? ga.data_ptr<float>() : sq.data_ptr<float>(),
-                     has_mom ? mom.data_ptr<float>() : sq.data_ptr<float>(),
-                     n, (float)lr, (float)alpha, (float)eps, (float)wd,
-                     (float)mu, centered, has_mom);
+  float* ga_ptr = centered ? ga.data_ptr<float>() : sq.data_ptr<float>();
+  float* mom_ptr = has_mom ? mom.data_ptr<float>() : sq.data_ptr<float>();
+  const bool fused = g_bf16.has_value() || p_bf16.has_value();
+  if (!fused) {
+    TORCH_CHECK(g.numel() == n, "rmsprop_step: grad size mismatch");
+    hipLaunchKernelGGL((rmsprop_step_kernel<false, false>),
+                       dim3(grid_for(n, 4)), dim3(kBlock), 0, cur_stream(),
+                       p.data_ptr<float>(), g.data_ptr<float>(),
+                       sq.data_ptr<float>(), ga_ptr, mom_ptr, n, (float)lr,
+                       (float)alpha, (float)eps, (float)wd, (float)mu, centered,
+                       has_mom, (const __bf16*)nullptr, 1.0f,
+                       (__bf16*)nullptr);
+    return;
+  }
+  // fused tail: bf16 gradient source and bf16 parameter shadow together
+  // (g is not read and may be empty)
+  TORCH_CHECK(g_bf16.has_value() && p_bf16.has_value(),
+              "rmsprop_step: the fused tail takes g_bf16 AND p_bf16");
+  TORCH_CHECK(g_bf16->scalar_type() == torch::kBFloat16 &&
+              p_bf16->scalar_type() == torch::kBFloat16 &&
+              g_bf16->numel() == n && p_bf16->numel() == n &&
+              g_bf16->is_contiguous() && p_bf16->is_contiguous() &&
+              p.is_contiguous() && sq.numel() == n);
+  const __bf16* gb = (const __bf16*)g_bf16->data_ptr();
+  __bf16* pb = (__bf16*)p_bf16->data_ptr();
+  if (grad_scale != 1.0)
+    hipLaunchKernelGGL((rmsprop_step_kernel<true, true>),
+                       dim3(grid_for(n, 4)), dim3(kBlock), 0, cur_stream(),
+                       p.data_ptr<float>(), (const float*)nullptr,
+                       sq.data_ptr<float>(), ga_ptr, mom_ptr, n, (float)lr,
+                       (float)alpha, (float)eps, (float)wd, (float)mu, centered,
+                       has_mom, gb, (float)grad_scale, pb);
+  else
+    hipLaunchKernelGGL((rmsprop_step_kernel<true, false>),
+                       dim3(grid_for(n, 4)), dim3(kBlock), 0, cur_stream(),
+                       p.data_ptr<float>(), (const float*)nullptr,
+                       sq.data_ptr<float>(), ga_ptr, mom_ptr, n, (float)lr,
+                       (float)alpha, (float)eps, (float)wd, (float)mu, centered,
+                       has_mom, gb, 1.0f, pb);
 }
 
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -2343,6 +2411,11 @@ bool lstm_seq_bwd_bf16(torch::Tensor dh_init, torch::Tensor gout,
 // reduce chain (~11 launches -> 3). h layout: the fused (B, 1024) hidden
 // [adv-stream | val-stream] produced by the single w1 GEMM
 // (ApexLearner._build_fast_forward).
+// PRE (pre-activation mode): h_* are the RAW outputs of the w1 GEMM and the
+// FC layer's ReLU happens here — max(x, 0) on the fragments as they load
+// (ReLU commutes with the bf16->fp32 load), dh written as 0 where h_s <= 0
+// (= threshold_backward of the bf16 dh). Bit-identical to feeding relu(h),
+// without the three clamp launches and the threshold launch per step.
 // ===========================================================================
 namespace {
 
@@ -2352,7 +2425,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-template <int HH, int A>  // HH = per-stream hidden (512), A = actions (6)
+__device__ __forceinline__ float relu_if(bool pre, float x) {
+  return pre ? (x > 0.0f ? x : 0.0f) : x;
+}
+
+// HH = per-stream hidden (512), A = actions (6)
+template <int HH, int A, bool PRE>
 __global__ __launch_bounds__(256) void dueling_q_loss_fwd_kernel(
     const __bf16* __restrict__ h_s,   // (B, 2*HH)
     const __bf16* __restrict__ h_on,  // (B, 2*HH)
@@ -2375,12 +2453,15 @@ __global__ __launch_bounds__(256) void dueling_q_loss_fwd_kernel(
   float ha_s[8], hv_s[8], ha_on[8], hv_on[8], ha_tg[8], hv_tg[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    ha_s[j] = (float)h_s[(int64_t)b * 2 * HH + k8 + j];
-    hv_s[j] = (float)h_s[(int64_t)b * 2 * HH + HH + k8 + j];
-    ha_on[j] = (float)h_on[(int64_t)b * 2 * HH + k8 + j];
-    hv_on[j] = (float)h_on[(int64_t)b * 2 * HH + HH + k8 + j];
-    ha_tg[j] = (float)h_tg[(int64_t)b * 2 * HH + k8 + j];
-    hv_tg[j] = (float)h_tg[(int64_t)b * 2 * HH + HH + k8 + j];
+    ha_s[j] = relu_if(PRE, (float)h_s[(int64_t)b * 2 * HH + k8 + j]);
+    hv_s[j] =
+        relu_if(PRE, (float)h_s[(int64_t)b * 2 * HH + HH + k8 + j]);
+    ha_on[j] = relu_if(PRE, (float)h_on[(int64_t)b * 2 * HH + k8 + j]);
+    hv_on[j] =
+        relu_if(PRE, (float)h_on[(int64_t)b * 2 * HH + HH + k8 + j]);
+    ha_tg[j] = relu_if(PRE, (float)h_tg[(int64_t)b * 2 * HH + k8 + j]);
+    hv_tg[j] =
+        relu_if(PRE, (float)h_tg[(int64_t)b * 2 * HH + HH + k8 + j]);
   }
   float q_s[A], q_on[A], q_tg[A];  // adv dots (bias added on lane 0 later)
 #pragma unroll
@@ -2444,11 +2525,12 @@ __global__ __launch_bounds__(256) void dueling_q_loss_fwd_kernel(
   }
 }
 
-template <int HH, int A>
+template <int HH, int A, bool PRE>
 __global__ void dueling_q_loss_bwd_dh_kernel(
     const float* __restrict__ grad_coef, const int64_t* __restrict__ act,
     const float* __restrict__ gout, const __bf16* __restrict__ wa,
-    const __bf16* __restrict__ wv, int B, __bf16* __restrict__ dh) {
+    const __bf16* __restrict__ wv, const __bf16* __restrict__ h_s, int B,
+    __bf16* __restrict__ dh) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * 2 * HH) return;
   const int b = i / (2 * HH);
@@ -2463,13 +2545,16 @@ __global__ void dueling_q_loss_bwd_dh_kernel(
   } else {
     v = c * (float)wv[k - HH];
   }
+  if constexpr (PRE) {
+    if (!((float)h_s[i] > 0.0f)) v = 0.0f;
+  }
   dh[i] = (__bf16)v;
 }
 
 // phase 1: grid (A+1 head-rows, BS b-slices); block (j, s) accumulates its
 // b-slice's partial dW row (+ bias partial) into the fp32 workspace
 // ws[(A+1) rows x (HH+1)] x BS. phase 2 folds the BS partials and casts.
-template <int HH, int A, int BS>
+template <int HH, int A, int BS, bool PRE>
 __global__ __launch_bounds__(256) void dueling_q_loss_bwd_dw_kernel(
     const float* __restrict__ grad_coef, const int64_t* __restrict__ act,
     const float* __restrict__ gout, const __bf16* __restrict__ h_s, int B,
@@ -2497,7 +2582,7 @@ __global__ __launch_bounds__(256) void dueling_q_loss_bwd_dw_kernel(
 #pragma unroll
     for (int u = 0; u < HH / 256; ++u) {
       const int k = u * 256 + tid;
-      accw[u] += alpha_jb * (float)h_s[hoff + k];
+      accw[u] += alpha_jb * relu_if(PRE, (float)h_s[hoff + k]);
     }
   }
   float* row = ws + ((int64_t)sl * (A + 1) + j) * (HH + 1);
@@ -2541,10 +2626,11 @@ void dueling_q_loss_fwd(torch::Tensor h_s, torch::Tensor h_on,
                         torch::Tensor rew, torch::Tensor done, torch::Tensor w,
                         double gamma_n, double alpha, torch::Tensor loss_out,
                         torch::Tensor prio_out, torch::Tensor grad_coef,
-                        torch::Tensor qmax_out) {
+                        torch::Tensor qmax_out, bool pre_act) {
   int B = (int)h_s.size(0);
   TORCH_CHECK(h_s.size(1) == 1024 && wa.size(0) == 6, "geometry: HH=512 A=6");
-  hipLaunchKernelGGL((dueling_q_loss_fwd_kernel<512, 6>),
+  hipLaunchKernelGGL((pre_act ? dueling_q_loss_fwd_kernel<512, 6, true>
+                              : dueling_q_loss_fwd_kernel<512, 6, false>),
                      dim3((B + 3) / 4), dim3(256), 0, cur_stream(),
                      (const __bf16*)h_s.data_ptr(),
                      (const __bf16*)h_on.data_ptr(),
@@ -2565,19 +2651,22 @@ void dueling_q_loss_bwd(torch::Tensor grad_coef, torch::Tensor act,
                         torch::Tensor gout, torch::Tensor wa, torch::Tensor wv,
                         torch::Tensor h_s, torch::Tensor dh, torch::Tensor dwa,
                         torch::Tensor dba, torch::Tensor dwv,
-                        torch::Tensor dbv) {
+                        torch::Tensor dbv, bool pre_act) {
   int B = (int)h_s.size(0);
-  hipLaunchKernelGGL((dueling_q_loss_bwd_dh_kernel<512, 6>),
+  TORCH_CHECK(h_s.numel() == (int64_t)B * 1024 && dh.numel() == h_s.numel());
+  hipLaunchKernelGGL((pre_act ? dueling_q_loss_bwd_dh_kernel<512, 6, true>
+                              : dueling_q_loss_bwd_dh_kernel<512, 6, false>),
                      dim3(ceil_div((int64_t)B * 1024, kBlock)), dim3(kBlock),
                      0, cur_stream(), grad_coef.data_ptr<float>(),
                      act.data_ptr<int64_t>(), gout.data_ptr<float>(),
                      (const __bf16*)wa.data_ptr(), (const __bf16*)wv.data_ptr(),
-                     B, (__bf16*)dh.data_ptr());
+                     (const __bf16*)h_s.data_ptr(), B, (__bf16*)dh.data_ptr());
   constexpr int BS = 32;  // b-slices (serial-B measured 16 us; 16 slices
                           // still left 32 serial iterations per block)
   auto ws = torch::empty({BS * 7 * 513}, torch::dtype(torch::kFloat32)
                                              .device(h_s.device()));
-  hipLaunchKernelGGL((dueling_q_loss_bwd_dw_kernel<512, 6, BS>),
+  hipLaunchKernelGGL((pre_act ? dueling_q_loss_bwd_dw_kernel<512, 6, BS, true>
+                              : dueling_q_loss_bwd_dw_kernel<512, 6, BS, false>),
                      dim3(7, BS), dim3(256), 0, cur_stream(),
                      grad_coef.data_ptr<float>(), act.data_ptr<int64_t>(),
                      gout.data_ptr<float>(), (const __bf16*)h_s.data_ptr(), B,

@@ -48,6 +48,21 @@ class FlatRMSprop(_FlatOptimBase):
             ext.rmsprop_step(p, g, sq, ga, mom, self.lr, self.alpha, self.eps,
                              self.wd, self.mu, self.centered, self.mu > 0)
 
+    def step_mixed(self, grads_bf16, params_bf16, grad_scale: float = 1.0):
+        """step() with the mixed-precision plumbing folded into the same
+        pass: gradients are read from the bf16 compute-grad flats (upcast,
+        times ``grad_scale`` when it is not 1) instead of ``self.grads``, and
+        each updated master is also written to its bf16 compute-param flat.
+        Bit-identical to upcast -> step() -> param sync; ``self.grads`` is
+        neither read nor written."""
+        ext = hip_ext()
+        for p, sq, ga, mom, gb, pb in zip(self.params, self.sq, self.ga,
+                                          self.mom, grads_bf16, params_bf16):
+            ext.rmsprop_step(p, p, sq, ga, mom, self.lr, self.alpha, self.eps,
+                             self.wd, self.mu, self.centered, self.mu > 0,
+                             g_bf16=gb, grad_scale=float(grad_scale),
+                             p_bf16=pb)
+
     def state_dict(self):
         return {"kind": "flat_rmsprop", "sq": self.sq, "ga": self.ga,
                 "mom": self.mom}

@@ -235,6 +235,27 @@ class MixedPrecisionTrainer:
         for g in self.groups:
             g.flat_cparam.copy_(g.flat_mparam)
 
+    def fused_step(self, optim) -> bool:
+        """upcast_grads() + optim.step() + sync_compute_params() as ONE
+        kernel when ``optim`` is the fused flat RMSprop over a single
+        compute-dtype (bf16) group: the optimizer reads the bf16 grad flat
+        directly (scaled by 1/world when distributed, like upcast_grads)
+        and writes the bf16 param flat next to the fp32 master. Returns
+        False (nothing done) for any other trainer/optimizer pair — callers
+        that touch flat_mgrad between upcast and step (grad clipping) must
+        keep the three-call sequence."""
+        from .flat_optim import FlatRMSprop
+
+        if not (isinstance(optim, FlatRMSprop) and len(self.groups) == 1
+                and self.groups[0].dtype == torch.bfloat16
+                and len(optim.params) == 1
+                and optim.params[0] is self.groups[0].flat_mparam):
+            return False
+        g = self.groups[0]
+        optim.step_mixed([g.flat_cgrad], [g.flat_cparam],
+                         1.0 / self.world if self.world > 1 else 1.0)
+        return True
+
     def broadcast_master(self):
         if self.world > 1:
             for g in self.groups:
