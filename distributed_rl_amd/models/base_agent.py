@@ -73,91 +73,76 @@ class CNN2D(nn.Module):
         )
         self._fused_checked: dict = {}
 
-    def _fused_ok(self, x: torch.Tensor) -> bool:
-        """Use the hand-written MFMA conv kernels (ops/hip/conv_mfma.hip)
-        when the whole stack's geometry is covered and weights are bf16
-        channels_last on a GPU."""
+    def _plan(self, x: torch.Tensor, grouped: bool = False):
+        """The fused path for x through the hand-written MFMA conv kernels
+        (ops/hip/conv_mfma.hip): one (stride, chw_out) per conv, or False
+        when x or the weights are not what the kernels take or a layer's
+        geometry has no kernel (grouped: no grouped kernel). The last conv
+        of a flattening stack writes the 2-D CHW-ordered output directly
+        (flatten fused into the epilogue) where the geometry has that
+        variant. Cached per input shape and dtype in _fused_checked."""
         if not (self._fusable_static and x.is_cuda):
             return False
         if x.dtype not in (torch.uint8, torch.bfloat16):
             return False
         key = (tuple(x.shape[1:]), x.dtype)
+        if grouped:
+            key = ("grouped",) + key
         hit = self._fused_checked.get(key)
         if hit is not None:
             return hit
         from .. import ops as _ops
 
-        ok = self._convs[0].weight.dtype == torch.bfloat16 and x.is_contiguous(
-            memory_format=torch.channels_last
-        )
-        if ok:
+        plan = []
+        if not (self._convs[0].weight.dtype == torch.bfloat16
+                and x.is_contiguous(memory_format=torch.channels_last)):
+            plan = False
+        else:
             C, H, W = x.shape[1:]
             u8 = x.dtype == torch.uint8
             for conv in self._convs:
                 COUT, _, KH, KW = conv.weight.shape
                 S = conv.stride[0]
-                if not _ops.conv_supported(H, W, C, KH, KW, S, COUT, u8):
-                    ok = False
+                geom = (H, W, C, KH, KW, S, COUT, u8)
+                chw = (conv is self._convs[-1] and self.flatten
+                       and _ops.conv_supported(*geom, chw_out=True))
+                if not _ops.conv_supported(*geom, chw_out=chw,
+                                           njobs=2 if grouped else 1):
+                    plan = False
                     break
+                plan.append((S, chw))
                 H = (H - KH) // S + 1
                 W = (W - KW) // S + 1
                 C = COUT
                 u8 = False
-        self._fused_checked[key] = ok
-        return ok
+        self._fused_checked[key] = plan
+        return plan
+
+    def _fused_ok(self, x: torch.Tensor) -> bool:
+        """Use the hand-written MFMA conv kernels when the whole stack's
+        geometry is covered and weights are bf16 channels_last on a GPU."""
+        return bool(self._plan(x))
+
+    def _grouped_ok(self, x: torch.Tensor) -> bool:
+        """_fused_ok plus a grouped kernel variant for every layer."""
+        return self._fused_ok(x) and bool(self._plan(x, grouped=True))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if self._fused_ok(x):
+        plan = self._plan(x)
+        if plan:
             from .. import ops as _ops
 
             y = x
-            last = len(self._convs) - 1
-            for i, conv in enumerate(self._convs):
-                # last conv of a flattening stack writes the 2-D CHW-ordered
-                # output directly (flatten fused into the epilogue)
-                if i == last and self.flatten and _ops.conv_chw_supported(
-                        y.shape[2], y.shape[3], y.shape[1],
-                        conv.weight.shape[2], conv.weight.shape[3],
-                        conv.stride[0], conv.weight.shape[0]):
-                    return _ops.fused_conv_relu(y, conv.weight, conv.bias,
-                                                conv.stride[0], chw_out=True)
-                y = _ops.fused_conv_relu(y, conv.weight, conv.bias,
-                                         conv.stride[0])
+            for conv, (stride, chw) in zip(self._convs, plan):
+                y = _ops.fused_conv_relu(y, conv.weight, conv.bias, stride,
+                                         chw_out=chw)
+            if chw:
+                return y
         else:
             y = self.body(x)
         if self.flatten:
             y = torch.flatten(y, 1)
         return y
-
-    def _grouped_ok(self, x: torch.Tensor) -> bool:
-        """_fused_ok plus a grouped kernel variant for every layer."""
-        if not self._fused_ok(x):
-            return False
-        key = ("grouped", tuple(x.shape[1:]), x.dtype)
-        hit = self._fused_checked.get(key)
-        if hit is not None:
-            return hit
-        from .. import ops as _ops
-
-        ok = True
-        C, H, W = x.shape[1:]
-        u8 = x.dtype == torch.uint8
-        last = len(self._convs) - 1
-        for i, conv in enumerate(self._convs):
-            COUT, _, KH, KW = conv.weight.shape
-            S = conv.stride[0]
-            chw = (i == last and self.flatten
-                   and _ops.conv_chw_supported(H, W, C, KH, KW, S, COUT))
-            if not _ops.conv_grouped_supported(H, W, C, KH, KW, S, COUT, u8,
-                                               chw):
-                ok = False
-                break
-            H = (H - KH) // S + 1
-            W = (W - KW) // S + 1
-            C = COUT
-            u8 = False
-        self._fused_checked[key] = ok
-        return ok
 
     @staticmethod
     def forward_grouped(jobs) -> List[torch.Tensor]:
@@ -193,18 +178,12 @@ class CNN2D(nn.Module):
             return t if needs_grad or t is None else t.detach()
 
         ys = [x if g else x.detach() for x, _, g in jobs]
-        last = len(m0._convs) - 1
-        for i in range(len(m0._convs)):
+        for i, (stride, chw) in enumerate(m0._plan(xs[0], grouped=True)):
             convs = [m._convs[i] for m in mods]
-            c0 = convs[0]
-            chw = (i == last and m0.flatten and _ops.conv_chw_supported(
-                ys[0].shape[2], ys[0].shape[3], ys[0].shape[1],
-                c0.weight.shape[2], c0.weight.shape[3], c0.stride[0],
-                c0.weight.shape[0]))
             ys = list(_ops.fused_conv_relu_grouped(
                 ys, [par(c.weight, j[2]) for c, j in zip(convs, jobs)],
                 [par(c.bias, j[2]) for c, j in zip(convs, jobs)],
-                c0.stride[0], chw_out=chw))
+                stride, chw_out=chw))
             if chw:
                 return ys
         if m0.flatten:

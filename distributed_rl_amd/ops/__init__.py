@@ -89,57 +89,19 @@ def dequant_frames_nhwc(x_u8: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 
 
-def conv_supported(H, W, C, KH, KW, S, COUT, u8: bool) -> bool:
+def conv_supported(H, W, C, KH, KW, S, COUT, u8: bool, chw_out: bool = False,
+                   njobs: int = 1) -> bool:
+    """Is there a fused forward for this geometry with this output form
+    (chw_out: flatten fused into the epilogue) for njobs jobs per launch?"""
     ext = hip_ext(required=False)
-    if ext is None:
-        return False
-    return bool(ext.conv_fwd_supported(H, W, C, KH, KW, S, COUT, u8))
-
-
-class _FusedConvFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, chw_out=False):
-        ext = hip_ext()
-        N, C, H, W = x.shape
-        COUT, _, KH, KW = weight.shape
-        P = (H - KH) // stride + 1
-        Q = (W - KW) // stride + 1
-        b = bias if bias is not None else torch.empty(0, device=x.device)
-        if chw_out:
-            # flatten fused into the epilogue: 2-D (N, COUT*P*Q) out in
-            # logical-NCHW element order (= torch.flatten of the 4-D out)
-            out = torch.empty(N, COUT * P * Q, dtype=torch.bfloat16,
-                              device=x.device)
-            ext.conv_fwd_chw(x, weight, b, out, stride)
-        else:
-            out = torch.empty(
-                N, COUT, P, Q, dtype=torch.bfloat16, device=x.device,
-                memory_format=torch.channels_last,
-            )
-            ext.conv_fwd(x, weight, b, out, stride)
-        ctx.save_for_backward(x, weight, out)
-        ctx.stride = stride
-        ctx.has_bias = bias is not None
-        ctx.chw = chw_out
-        ctx.pq = (P, Q)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        x, weight, out = ctx.saved_tensors
-        need_x = ctx.needs_input_grad[0]
-        need_w = ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        gi, gw, gb = _fused_conv_backward(
-            x, weight, out, gout, ctx.stride, ctx.has_bias, ctx.chw, ctx.pq,
-            need_x, need_w, need_b)
-        return gi, gw, gb, None, None
+    return ext is not None and bool(
+        ext.conv_fwd_supported(H, W, C, KH, KW, S, COUT, u8, chw_out, njobs))
 
 
 def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
                          need_x, need_w, need_b):
-    """Backward of one fused conv+bias+ReLU layer; returns (gi, gw, gb).
-    Shared by _FusedConvFn and _FusedConvGroupedFn."""
+    """Backward of one fused conv+bias+ReLU layer (one job of
+    _FusedConvGroupedFn); returns (gi, gw, gb)."""
     COUT = weight.shape[0]
     if chw:
         # one kernel: relu-mask + CHW->NHWC transpose
@@ -200,7 +162,6 @@ def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
     use_own_dgrad = (
         os.environ.get("DRL_OWN_DGRAD", "0") == "1"
         and need_x and x.dtype == torch.bfloat16
-        and hasattr(ext, "conv_dgrad_supported")
         and bool(ext.conv_dgrad_supported(x.shape[2], x.shape[3], C, KH,
                                           KW, stride, COUT))
     )
@@ -233,25 +194,12 @@ def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
     return (gi if need_x else None), gw, gb
 
 
-def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
-    """One fused conv+bias+ReLU layer (u8 or bf16 channels_last input).
-    chw_out=True additionally fuses the trailing flatten into the epilogue
-    (returns 2-D (N, COUT*P*Q) in logical-NCHW order)."""
-    return _FusedConvFn.apply(x, weight, bias, stride, chw_out)
-
-
-def conv_grouped_supported(H, W, C, KH, KW, S, COUT, u8: bool,
-                           chw_out: bool = False) -> bool:
-    ext = hip_ext(required=False)
-    return ext is not None and hasattr(ext, "conv_fwd_grouped_supported") and \
-        bool(ext.conv_fwd_grouped_supported(H, W, C, KH, KW, S, COUT, u8,
-                                            chw_out))
-
-
 class _FusedConvGroupedFn(torch.autograd.Function):
-    """Several independent same-geometry conv+bias+ReLU layers (e.g. the
+    """One to four independent same-geometry conv+bias+ReLU layers (e.g. the
     online(s), online(s'), target(s') forwards of one Ape-X step) in ONE
     launch. args = xs + weights + biases (biases all None or all tensors).
+    chw_out fuses the trailing flatten into the epilogue: the outputs are
+    2-D (N, COUT*P*Q) in logical-NCHW order (= torch.flatten of the 4-D out).
     The backward runs the single-job backward for the jobs whose inputs or
     parameters require grad; the other jobs' outputs are non-differentiable."""
 
@@ -333,6 +281,14 @@ def fused_conv_relu_grouped(xs, weights, biases, stride: int,
                                      *biases)
 
 
+def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
+    """One fused conv+bias+ReLU layer (u8 or bf16 channels_last input).
+    chw_out=True additionally fuses the trailing flatten into the epilogue
+    (returns 2-D (N, COUT*P*Q) in logical-NCHW order)."""
+    return _FusedConvGroupedFn.apply(stride, bool(chw_out), 1, x, weight,
+                                     bias)[0]
+
+
 # ---------------------------------------------------------------------------
 # K2b — fused MFMA 3x3 stride-1 pad-1 conv for the IMPALA-ResNet torso
 # (relu_in / bias / residual / relu_out fused; aten backward)
@@ -341,8 +297,7 @@ def fused_conv_relu_grouped(xs, weights, biases, stride: int,
 
 def conv3x3_supported(H, W, C, COUT) -> bool:
     ext = hip_ext(required=False)
-    return ext is not None and hasattr(ext, "conv3x3p1_supported") and \
-        bool(ext.conv3x3p1_supported(H, W, C, COUT))
+    return ext is not None and bool(ext.conv3x3p1_supported(H, W, C, COUT))
 
 
 class _FusedConv3x3Fn(torch.autograd.Function):
@@ -410,12 +365,6 @@ def fused_conv3x3(x, weight, bias, *, relu_in: bool = False,
         return _FusedConv3x3Fn.apply(x, weight, bias, residual, bool(relu_in),
                                      bool(relu_out))
     return torch_ref.conv3x3_res(x, weight, bias, relu_in, relu_out, residual)
-
-
-def conv_chw_supported(H, W, C, KH, KW, S, COUT) -> bool:
-    ext = hip_ext(required=False)
-    return ext is not None and hasattr(ext, "conv_fwd_chw_supported") and \
-        bool(ext.conv_fwd_chw_supported(H, W, C, KH, KW, S, COUT))
 
 
 def linear_relu_supported(K, N) -> bool:

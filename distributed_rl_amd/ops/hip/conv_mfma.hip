@@ -206,65 +206,6 @@ __global__ __launch_bounds__(WAVES * 64) void conv_fwd_grouped_kernel(
       tile, reinterpret_cast<__bf16*>(smem));
 }
 
-struct ConvLaunch {
-  int H, W, C, KH, KW, S, COUT;
-  bool u8;
-  void (*fn)(const void*, const __bf16*, const __bf16*, __bf16*, int);
-  int lds_bytes;
-  int waves, rpw;
-  void (*grouped)(const ConvJobs, int, int);  // null: no grouped variant
-};
-
-template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8,
-          int WAVES = 4, int RPW = 16, bool CHW = false, bool GROUPED = false>
-ConvLaunch make_launch() {
-  using G = ConvGeom<H, W, C, KH, KW, S, COUT, U8>;
-  void (*grouped)(const ConvJobs, int, int) = nullptr;
-  if constexpr (GROUPED)
-    grouped = conv_fwd_grouped_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW,
-                                      CHW>;
-  return ConvLaunch{H, W, C, KH, KW, S, COUT, U8,
-                    conv_fwd_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW,
-                                    CHW>,
-                    (int)(G::LDS_ELEMS * sizeof(__bf16)), WAVES, RPW, grouped};
-}
-
-// CHW-out variants for the stack-final conv of each model (flatten fusion)
-static const ConvLaunch kChwLaunches[] = {
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16, true, true>(),
-    make_launch<20, 20, 16, 4, 4, 2, 32, false, 8, 16, true>(),
-};
-
-static const ConvLaunch kLaunches[] = {
-    // Ape-X / R2D2 stack (cfg/ape_x.json:38-51); WAVES/RPW picked by the
-    // variant sweep in tools/gpu_conv_tune.py (profiles/)
-    // (these four also carry the grouped variant)
-    make_launch<84, 84, 4, 8, 8, 4, 32, true, 8, 32, false, true>(),
-    make_launch<84, 84, 4, 8, 8, 4, 32, false, 8, 32, false, true>(),
-    make_launch<20, 20, 32, 4, 4, 2, 64, false, 8, 16, false, true>(),
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16, false, true>(),
-    // IMPALA stack (cfg/impala.json:26-39)
-    make_launch<84, 84, 4, 8, 8, 4, 16, true, 8, 16>(),
-    make_launch<84, 84, 4, 8, 8, 4, 16, false, 8, 16>(),
-    make_launch<20, 20, 16, 4, 4, 2, 32, false, 8, 16>(),
-};
-
-// variant table for on-GPU tuning (tools/gpu_conv_tune.py)
-static const ConvLaunch kVariants[] = {
-    make_launch<84, 84, 4, 8, 8, 4, 32, true, 4, 16>(),
-    make_launch<84, 84, 4, 8, 8, 4, 32, true, 8, 16>(),
-    make_launch<84, 84, 4, 8, 8, 4, 32, true, 4, 32>(),
-    make_launch<84, 84, 4, 8, 8, 4, 32, true, 8, 32>(),
-    make_launch<20, 20, 32, 4, 4, 2, 64, false, 4, 16>(),
-    make_launch<20, 20, 32, 4, 4, 2, 64, false, 8, 16>(),
-    make_launch<20, 20, 32, 4, 4, 2, 64, false, 4, 32>(),
-    make_launch<20, 20, 32, 4, 4, 2, 64, false, 8, 32>(),
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 4, 16>(),
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 16>(),
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 4, 32>(),
-    make_launch<9, 9, 64, 3, 3, 1, 64, false, 8, 32>(),
-};
-
 // Layout probe: C(16,16) = A(16,32) x B(32,16) with exactly the fragment
 // maps documented above — unit-tested against torch.matmul on the GPU so a
 // map error fails loudly instead of silently transposing outputs.
@@ -287,159 +228,6 @@ __global__ void mfma_probe_kernel(const __bf16* __restrict__ A,
 }
 
 }  // namespace
-
-void mfma_probe(torch::Tensor A, torch::Tensor B, torch::Tensor C) {
-  hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const __bf16*)A.data_ptr(), (const __bf16*)B.data_ptr(),
-                     C.data_ptr<float>());
-}
-
-// Returns true if a fused kernel exists for this geometry.
-bool conv_fwd_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
-                        int64_t S, int64_t COUT, bool u8) {
-  for (const auto& l : kLaunches)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == S && l.COUT == COUT && l.u8 == u8)
-      return true;
-  return false;
-}
-
-// in: (N,C,H,W) logical, channels_last (or uint8 NCHW-contiguous when u8 —
-// then treated as NHWC? no: u8 input must also be channels_last). weight:
-// (COUT,C,KH,KW) logical channels_last. bias: (COUT) f32 or undefined.
-// out: (N,COUT,P,Q) logical channels_last bf16.
-void conv_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
-              torch::Tensor out, int64_t stride) {
-  TORCH_CHECK(in.is_cuda() && out.is_cuda());
-  TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_fwd input must be channels_last");
-  TORCH_CHECK(out.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(weight.is_contiguous(at::MemoryFormat::ChannelsLast));
-  const int N = (int)in.size(0), C = (int)in.size(1), H = (int)in.size(2),
-            W = (int)in.size(3);
-  const int COUT = (int)weight.size(0), KH = (int)weight.size(2),
-            KW = (int)weight.size(3);
-  const bool u8 = in.scalar_type() == torch::kUInt8;
-  if (!u8) TORCH_CHECK(in.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(weight.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16);
-  const ConvLaunch* L = nullptr;
-  for (const auto& l : kLaunches)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == (int)stride && l.COUT == COUT && l.u8 == u8) {
-      L = &l;
-      break;
-    }
-  TORCH_CHECK(L, "no fused conv kernel for this geometry: ", H, "x", W, "x", C,
-              " k", KH, "x", KW, " s", stride, " -> ", COUT, " u8=", u8);
-  const int P = (H - KH) / (int)stride + 1, Q = (W - KW) / (int)stride + 1;
-  const int M = N * P * Q;
-  const int rows_per_block = L->waves * L->rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  const __bf16* bias_ptr = nullptr;
-  if (bias.defined() && bias.numel() > 0) {
-    TORCH_CHECK(bias.scalar_type() == torch::kBFloat16);
-    bias_ptr = (const __bf16*)bias.data_ptr();
-  }
-  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), L->lds_bytes,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const void*)in.data_ptr(),
-                     (const __bf16*)weight.data_ptr(), bias_ptr,
-                     (__bf16*)out.data_ptr(), N);
-}
-
-// Run a specific tuning variant (tools/gpu_conv_tune.py); returns false if
-// the variant index does not match the geometry.
-bool conv_fwd_variant(torch::Tensor in, torch::Tensor weight,
-                      torch::Tensor bias, torch::Tensor out, int64_t stride,
-                      int64_t variant) {
-  const int N = (int)in.size(0), C = (int)in.size(1), H = (int)in.size(2),
-            W = (int)in.size(3);
-  const int COUT = (int)weight.size(0), KH = (int)weight.size(2),
-            KW = (int)weight.size(3);
-  const bool u8 = in.scalar_type() == torch::kUInt8;
-  if (variant < 0 || variant >= (int64_t)(sizeof(kVariants) / sizeof(ConvLaunch)))
-    return false;
-  const ConvLaunch* L = &kVariants[variant];
-  if (!(L->H == H && L->W == W && L->C == C && L->KH == KH && L->KW == KW &&
-        L->S == (int)stride && L->COUT == COUT && L->u8 == u8))
-    return false;
-  const int P = (H - KH) / (int)stride + 1, Q = (W - KW) / (int)stride + 1;
-  const int M = N * P * Q;
-  const int rows_per_block = L->waves * L->rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  const __bf16* bias_ptr = nullptr;
-  if (bias.defined() && bias.numel() > 0)
-    bias_ptr = (const __bf16*)bias.data_ptr();
-  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), L->lds_bytes,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const void*)in.data_ptr(),
-                     (const __bf16*)weight.data_ptr(), bias_ptr,
-                     (__bf16*)out.data_ptr(), N);
-  return true;
-}
-
-void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
-              torch::Tensor gb_ws, int64_t stride);  // defined below
-bool conv_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                        int64_t KW, int64_t S, int64_t COUT, bool u8);
-void conv_dgrad(torch::Tensor gout, torch::Tensor weight, torch::Tensor w_t,
-                torch::Tensor dx, int64_t stride);  // defined below
-bool conv_dgrad_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                          int64_t KW, int64_t S, int64_t COUT);
-void conv_fwd_chw(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
-                  torch::Tensor out2d, int64_t stride);  // defined below
-bool conv_fwd_chw_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                            int64_t KW, int64_t S, int64_t COUT);
-void relu_mask_bwd_chw(torch::Tensor gout2d, torch::Tensor out2d,
-                       torch::Tensor dst_nhwc, int64_t C, int64_t PQ);
-void conv_fwd_grouped(std::vector<torch::Tensor> ins,
-                      std::vector<torch::Tensor> weights,
-                      std::vector<torch::Tensor> biases,
-                      std::vector<torch::Tensor> outs, int64_t stride,
-                      bool chw_out);  // defined below
-bool conv_fwd_grouped_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                                int64_t KW, int64_t S, int64_t COUT, bool u8,
-                                bool chw_out);
-void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
-                 torch::Tensor out);  // defined below
-bool linear_relu_supported(int64_t K, int64_t N);
-void tr16_probe(torch::Tensor out, int64_t mode);
-void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
-                   torch::Tensor residual, torch::Tensor out, bool relu_in,
-                   bool relu_out);  // defined below
-bool conv3x3p1_supported(int64_t H, int64_t W, int64_t C, int64_t COUT);
-
-void register_conv(pybind11::module_& m) {
-  m.def("conv_fwd", &conv_fwd,
-        "fused NHWC bf16 MFMA conv fwd (+dequant on u8 input, bias, ReLU)");
-  m.def("conv_fwd_supported", &conv_fwd_supported);
-  m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA fragment-map probe");
-  m.def("conv_fwd_variant", &conv_fwd_variant, "tuning-variant conv fwd");
-  m.def("conv_fwd_grouped", &conv_fwd_grouped,
-        "conv_fwd / conv_fwd_chw for up to 4 same-geometry jobs in one launch");
-  m.def("conv_fwd_grouped_supported", &conv_fwd_grouped_supported);
-  m.def("conv_wrw", &conv_wrw,
-        "MFMA conv weight-grad; gw/gb are fp32 workspaces or bf16 grads");
-  m.def("conv_wrw_supported", &conv_wrw_supported);
-  m.def("conv_dgrad", &conv_dgrad,
-        "MFMA conv data-grad (masked-tap gather, pre-transposed weights)");
-  m.def("conv_dgrad_supported", &conv_dgrad_supported);
-  m.def("conv_fwd_chw", &conv_fwd_chw,
-        "conv fwd with flatten fused into the epilogue (2-D CHW out)");
-  m.def("conv_fwd_chw_supported", &conv_fwd_chw_supported);
-  m.def("relu_mask_bwd_chw", &relu_mask_bwd_chw,
-        "relu-mask + CHW->NHWC transpose (backward of the fused flatten)");
-  m.def("linear_relu", &linear_relu,
-        "fused Linear+bias+ReLU fwd (own MFMA GEMM, LDS-staged W)");
-  m.def("linear_relu_supported", &linear_relu_supported);
-  m.def("tr16_probe", &tr16_probe);
-  m.def("conv3x3p1_fwd", &conv3x3p1_fwd,
-        "MFMA 3x3 s1 pad-1 NHWC bf16 conv fwd (+relu_in, bias, residual, "
-        "relu_out)");
-  m.def("conv3x3p1_supported", &conv3x3p1_supported);
-}
 
 // ===========================================================================
 // Weight-grad (wrw) kernel: gw[COUT][K] = sum_m gout^T[COUT][m] * im2col[m][K]
@@ -676,34 +464,6 @@ __global__ __launch_bounds__(256) void wrw_reduce_kernel(
   }
 }
 
-struct WrwLaunch {
-  int H, W, C, KH, KW, S, COUT;
-  bool u8;
-  void (*fn)(const void*, const __bf16*, float*, int, int);
-  int lds_bytes;
-  int ktiles;
-};
-
-template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8>
-WrwLaunch make_wrw() {
-  using G = ConvGeom<H, W, C, KH, KW, S, COUT, U8>;
-  static_assert(G::K % 64 == 0, "wrw needs K % 64 == 0");
-  return WrwLaunch{H, W, C, KH, KW, S, COUT, U8,
-                   conv_wrw_kernel<H, W, C, KH, KW, S, COUT, U8>,
-                   (int)(32 * (64 + kPadM + COUT + kPadM) * sizeof(__bf16)),
-                   G::K / 64};
-}
-
-static const WrwLaunch kWrwLaunches[] = {
-    make_wrw<84, 84, 4, 8, 8, 4, 32, true>(),
-    make_wrw<84, 84, 4, 8, 8, 4, 32, false>(),
-    make_wrw<20, 20, 32, 4, 4, 2, 64, false>(),
-    make_wrw<9, 9, 64, 3, 3, 1, 64, false>(),
-    make_wrw<84, 84, 4, 8, 8, 4, 16, true>(),
-    make_wrw<84, 84, 4, 8, 8, 4, 16, false>(),
-    make_wrw<20, 20, 16, 4, 4, 2, 32, false>(),
-};
-
 // bias grad: column sum of the (M, COUT) relu-masked gout — torch's
 // strided bf16 reduce on channels_last costs ~11 us; this is one pass with
 // an ordered block-level LDS reduction; each block writes its COUT partial
@@ -744,109 +504,6 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(
 
 }  // namespace
 
-bool conv_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
-                        int64_t S, int64_t COUT, bool u8) {
-  for (const auto& l : kWrwLaunches)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == S && l.COUT == COUT && l.u8 == u8)
-      return true;
-  return false;
-}
-
-// in: (N,C,H,W) channels_last u8/bf16; gout: (N,COUT,P,Q) channels_last bf16
-// (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 and gb_ws: (COUT) fp32
-// (or empty), both fully overwritten. bf16 gw_ws/gb_ws are the gradients
-// themselves: gw_ws then holds COUT*KH*KW*C elements in (cout, kh, kw, c)
-// memory order (a channels_last weight-shaped tensor or its flat view).
-void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
-              torch::Tensor gb_ws, int64_t stride) {
-  TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(gout.is_contiguous(at::MemoryFormat::ChannelsLast));
-  const bool bf16_out = gw_ws.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(bf16_out || gw_ws.scalar_type() == torch::kFloat32);
-  TORCH_CHECK(gw_ws.is_contiguous() ||
-              (gw_ws.dim() == 4 &&
-               gw_ws.is_contiguous(at::MemoryFormat::ChannelsLast)));
-  const int N = (int)in.size(0), C = (int)in.size(1), H = (int)in.size(2),
-            W = (int)in.size(3);
-  const int COUT = (int)gout.size(1);
-  const bool u8 = in.scalar_type() == torch::kUInt8;
-  const WrwLaunch* L = nullptr;
-  for (const auto& l : kWrwLaunches) {
-    int KHl = l.KH, KWl = l.KW;
-    if (l.H == H && l.W == W && l.C == C && l.S == (int)stride &&
-        l.COUT == COUT && l.u8 == u8 &&
-        (H - KHl) / (int)stride + 1 == (int)gout.size(2) &&
-        (W - KWl) / (int)stride + 1 == (int)gout.size(3)) {
-      L = &l;
-      break;
-    }
-  }
-  TORCH_CHECK(L, "no wrw kernel for this geometry");
-  const int P = (int)gout.size(2), Q = (int)gout.size(3);
-  const int M = N * P * Q;
-  const int n_chunks = (M + 31) / 32;
-  // scale the m-grid with the batch: R2D2/IMPALA run 8-20x Ape-X's row
-  // count through the same kernel (conv1 wrw measured 139 us at 1.02M
-  // rows with 512 blocks = 250 serial chunks per block)
-  int mb = (n_chunks > 8192 ? 2048 : 512) / L->ktiles;  // every m-slice costs one partial plane of write + read traffic
-  if (mb > n_chunks) mb = n_chunks;
-  if (mb < 1) mb = 1;
-  auto st = (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
-  const int n_elem = (int)gw_ws.numel();
-  TORCH_CHECK(n_elem == COUT * L->ktiles * 64, "gw_ws shape mismatch");
-  // per-m-slice partial planes (every (ktile, m-slice) block writes its
-  // whole 64 x COUT tile, so no zero-fill) + ordered reduction
-  const auto f32 = gw_ws.options().dtype(torch::kFloat32);
-  auto part = torch::empty({(int64_t)mb, (int64_t)n_elem + kPlanePad}, f32);
-  hipLaunchKernelGGL(L->fn, dim3(L->ktiles, mb), dim3(256), L->lds_bytes, st,
-                     (const void*)in.data_ptr(), (const __bf16*)gout.data_ptr(),
-                     part.data_ptr<float>(), N, mb);
-  const bool bias = gb_ws.defined() && gb_ws.numel() > 0;
-  constexpr int kColsumBlocks = 256;
-  torch::Tensor b_part;
-  if (bias) {
-    TORCH_CHECK(gb_ws.numel() == COUT && gb_ws.is_contiguous() &&
-                gb_ws.scalar_type() == gw_ws.scalar_type());
-    b_part = torch::empty({(int64_t)kColsumBlocks, (int64_t)COUT}, f32);
-    const int64_t Mrows = (int64_t)N * P * Q;
-    switch (COUT) {
-      case 16:
-        hipLaunchKernelGGL(colsum_bf16_kernel<16>, dim3(kColsumBlocks),
-                           dim3(256), 0, st, (const __bf16*)gout.data_ptr(),
-                           Mrows, b_part.data_ptr<float>());
-        break;
-      case 32:
-        hipLaunchKernelGGL(colsum_bf16_kernel<32>, dim3(kColsumBlocks),
-                           dim3(256), 0, st, (const __bf16*)gout.data_ptr(),
-                           Mrows, b_part.data_ptr<float>());
-        break;
-      case 64:
-        hipLaunchKernelGGL(colsum_bf16_kernel<64>, dim3(kColsumBlocks),
-                           dim3(256), 0, st, (const __bf16*)gout.data_ptr(),
-                           Mrows, b_part.data_ptr<float>());
-        break;
-      default:
-        TORCH_CHECK(false, "no colsum instantiation for COUT=", COUT);
-    }
-  }
-  const int e_blocks = (n_elem + 63) / 64;
-  const float* b_part_ptr =
-      bias ? (const float*)b_part.data_ptr<float>() : nullptr;
-  if (bf16_out)
-    hipLaunchKernelGGL(wrw_reduce_kernel<__bf16>,
-                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
-                       (const float*)part.data_ptr<float>(), mb, n_elem,
-                       (__bf16*)gw_ws.data_ptr(), b_part_ptr, kColsumBlocks,
-                       COUT, bias ? (__bf16*)gb_ws.data_ptr() : nullptr);
-  else
-    hipLaunchKernelGGL(wrw_reduce_kernel<float>,
-                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
-                       (const float*)part.data_ptr<float>(), mb, n_elem,
-                       gw_ws.data_ptr<float>(), b_part_ptr, kColsumBlocks, COUT,
-                       bias ? gb_ws.data_ptr<float>() : nullptr);
-}
-
 // tr16 semantics probe: fill LDS with 0..511, each lane passes base +
 // per-lane offset `mode`, dump what each lane's 4 elements are.
 namespace {
@@ -869,12 +526,6 @@ __global__ void tr16_probe_kernel(float* out, int mode) {
   for (int j = 0; j < 4; ++j) out[lane * 4 + j] = (float)v[j];
 }
 }  // namespace
-
-void tr16_probe(torch::Tensor out, int64_t mode) {
-  hipLaunchKernelGGL(tr16_probe_kernel, dim3(1), dim3(64), 0,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     out.data_ptr<float>(), (int)mode);
-}
 
 // ===========================================================================
 // Data-grad (dgrad) kernel — retires MIOpen igemm_bwd / ck grouped-bwd from
@@ -992,205 +643,7 @@ __global__ void conv_w_transpose_kernel(const __bf16* __restrict__ w,
   w_t[((int64_t)c * TAPS + tap) * COUT + co] = w[i];
 }
 
-struct DgradLaunch {
-  int H, W, C, KH, KW, S, COUT;
-  void (*fn)(const __bf16*, const __bf16*, __bf16*, int);
-  int waves, rpw;
-};
-
-template <int H, int W, int C, int KH, int KW, int S, int COUT, int WAVES = 8,
-          int RPW = 16>
-DgradLaunch make_dgrad() {
-  return DgradLaunch{H, W, C, KH, KW, S, COUT,
-                     conv_dgrad_kernel<H, W, C, KH, KW, S, COUT, WAVES, RPW>,
-                     WAVES, RPW};
-}
-
-static const DgradLaunch kDgrad[] = {
-    make_dgrad<20, 20, 32, 4, 4, 2, 64>(),  // apex/r2d2 conv2
-    make_dgrad<9, 9, 64, 3, 3, 1, 64>(),    // apex/r2d2 conv3
-    make_dgrad<20, 20, 16, 4, 4, 2, 32>(),  // impala conv2
-};
 }  // namespace
-
-bool conv_dgrad_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                          int64_t KW, int64_t S, int64_t COUT) {
-  for (const auto& l : kDgrad)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == S && l.COUT == COUT)
-      return true;
-  return false;
-}
-
-// gout: (N,COUT,P,Q) logical channels_last bf16; weight (COUT,C,KH,KW)
-// logical channels_last bf16; dx out (N,C,H,W) logical channels_last bf16;
-// w_t workspace (C*KH*KW*COUT) bf16.
-void conv_dgrad(torch::Tensor gout, torch::Tensor weight, torch::Tensor w_t,
-                torch::Tensor dx, int64_t stride) {
-  TORCH_CHECK(gout.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(dx.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(weight.is_contiguous(at::MemoryFormat::ChannelsLast));
-  const int N = (int)dx.size(0), C = (int)dx.size(1), H = (int)dx.size(2),
-            W = (int)dx.size(3);
-  const int COUT = (int)weight.size(0), KH = (int)weight.size(2),
-            KW = (int)weight.size(3);
-  const DgradLaunch* L = nullptr;
-  for (const auto& l : kDgrad)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == (int)stride && l.COUT == COUT) {
-      L = &l;
-      break;
-    }
-  TORCH_CHECK(L, "no dgrad kernel for this geometry");
-  auto stream = (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
-  const int total = KH * KW * C * COUT;
-  hipLaunchKernelGGL(conv_w_transpose_kernel, dim3((total + 255) / 256),
-                     dim3(256), 0, stream, (const __bf16*)weight.data_ptr(),
-                     (__bf16*)w_t.data_ptr(), KH * KW, C, COUT);
-  const int M = N * H * W;
-  const int rows_per_block = L->waves * L->rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), 0, stream,
-                     (const __bf16*)gout.data_ptr(),
-                     (const __bf16*)w_t.data_ptr(), (__bf16*)dx.data_ptr(), N);
-}
-
-// conv_fwd with the flatten fused into the epilogue (CHW-ordered 2-D out).
-bool conv_fwd_chw_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                            int64_t KW, int64_t S, int64_t COUT) {
-  for (const auto& l : kChwLaunches)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == S && l.COUT == COUT)
-      return true;
-  return false;
-}
-
-void conv_fwd_chw(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
-                  torch::Tensor out2d, int64_t stride) {
-  TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(weight.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(out2d.is_contiguous() && out2d.dim() == 2);
-  const int N = (int)in.size(0), C = (int)in.size(1), H = (int)in.size(2),
-            W = (int)in.size(3);
-  const int COUT = (int)weight.size(0), KH = (int)weight.size(2),
-            KW = (int)weight.size(3);
-  const ConvLaunch* L = nullptr;
-  for (const auto& l : kChwLaunches)
-    if (l.H == H && l.W == W && l.C == C && l.KH == KH && l.KW == KW &&
-        l.S == (int)stride && l.COUT == COUT) {
-      L = &l;
-      break;
-    }
-  TORCH_CHECK(L, "no CHW-out conv kernel for this geometry");
-  const int P = (H - KH) / (int)stride + 1, Q = (W - KW) / (int)stride + 1;
-  const int M = N * P * Q;
-  const int rows_per_block = L->waves * L->rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  const __bf16* bias_ptr = nullptr;
-  if (bias.defined() && bias.numel() > 0)
-    bias_ptr = (const __bf16*)bias.data_ptr();
-  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), L->lds_bytes,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const void*)in.data_ptr(),
-                     (const __bf16*)weight.data_ptr(), bias_ptr,
-                     (__bf16*)out2d.data_ptr(), N);
-}
-
-// Grouped conv_fwd / conv_fwd_chw: one launch for up to kMaxConvJobs jobs of
-// the same geometry and batch size (see conv_fwd_grouped_kernel). biases is
-// either empty (no job has a bias) or one tensor per job.
-void conv_fwd_grouped(std::vector<torch::Tensor> ins,
-                      std::vector<torch::Tensor> weights,
-                      std::vector<torch::Tensor> biases,
-                      std::vector<torch::Tensor> outs, int64_t stride,
-                      bool chw_out) {
-  const int njobs = (int)ins.size();
-  TORCH_CHECK(njobs >= 1 && njobs <= kMaxConvJobs, "1..", kMaxConvJobs,
-              " conv jobs per grouped launch");
-  TORCH_CHECK((int)weights.size() == njobs && (int)outs.size() == njobs &&
-              (biases.empty() || (int)biases.size() == njobs));
-  const auto& in0 = ins[0];
-  const auto& w0 = weights[0];
-  const int N = (int)in0.size(0), C = (int)in0.size(1), H = (int)in0.size(2),
-            W = (int)in0.size(3);
-  const int COUT = (int)w0.size(0), KH = (int)w0.size(2), KW = (int)w0.size(3);
-  const bool u8 = in0.scalar_type() == torch::kUInt8;
-  const int P = (H - KH) / (int)stride + 1, Q = (W - KW) / (int)stride + 1;
-  ConvJobs jobs{};
-  for (int j = 0; j < njobs; ++j) {
-    const auto& in = ins[j];
-    const auto& w = weights[j];
-    const auto& out = outs[j];
-    TORCH_CHECK(in.is_cuda() && w.is_cuda() && out.is_cuda());
-    TORCH_CHECK(in.dim() == 4 && in.sizes() == in0.sizes() &&
-                    in.scalar_type() == in0.scalar_type(),
-                "grouped conv jobs must share N and input geometry");
-    TORCH_CHECK(u8 || in.scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(w.dim() == 4 && w.sizes() == w0.sizes() && w.size(1) == C &&
-                    w.scalar_type() == torch::kBFloat16,
-                "grouped conv jobs must share the weight geometry");
-    TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_fwd_grouped input must be channels_last");
-    TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(out.scalar_type() == torch::kBFloat16 &&
-                out.numel() == (int64_t)N * COUT * P * Q);
-    if (chw_out) {
-      TORCH_CHECK(out.dim() == 2 && out.is_contiguous());
-    } else {
-      TORCH_CHECK(out.dim() == 4 && out.size(0) == N && out.size(1) == COUT &&
-                  out.size(2) == P && out.size(3) == Q &&
-                  out.is_contiguous(at::MemoryFormat::ChannelsLast));
-    }
-    jobs.in[j] = in.data_ptr();
-    jobs.weight[j] = (const __bf16*)w.data_ptr();
-    jobs.out[j] = (__bf16*)out.data_ptr();
-    jobs.bias[j] = nullptr;
-    if (!biases.empty() && biases[j].defined() && biases[j].numel() > 0) {
-      TORCH_CHECK(biases[j].scalar_type() == torch::kBFloat16 &&
-                  biases[j].numel() == COUT && biases[j].is_cuda());
-      jobs.bias[j] = (const __bf16*)biases[j].data_ptr();
-    }
-  }
-  const ConvLaunch* L = nullptr;
-  auto match = [&](const ConvLaunch& l) {
-    return l.grouped && l.H == H && l.W == W && l.C == C && l.KH == KH &&
-           l.KW == KW && l.S == (int)stride && l.COUT == COUT && l.u8 == u8;
-  };
-  if (chw_out) {
-    for (const auto& l : kChwLaunches)
-      if (match(l)) { L = &l; break; }
-  } else {
-    for (const auto& l : kLaunches)
-      if (match(l)) { L = &l; break; }
-  }
-  TORCH_CHECK(L, "no grouped conv kernel for this geometry: ", H, "x", W, "x",
-              C, " k", KH, "x", KW, " s", stride, " -> ", COUT, " u8=", u8,
-              " chw=", chw_out);
-  const int M = N * P * Q;
-  const int rows_per_block = L->waves * L->rpw;
-  const int tiles = (M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(L->grouped, dim3(tiles * njobs), dim3(L->waves * 64),
-                     L->lds_bytes,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     jobs, njobs, N);
-}
-
-bool conv_fwd_grouped_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                                int64_t KW, int64_t S, int64_t COUT, bool u8,
-                                bool chw_out) {
-  auto match = [&](const ConvLaunch& l) {
-    return l.grouped && l.H == H && l.W == W && l.C == C && l.KH == KH &&
-           l.KW == KW && l.S == S && l.COUT == COUT && l.u8 == u8;
-  };
-  if (chw_out) {
-    for (const auto& l : kChwLaunches)
-      if (match(l)) return true;
-  } else {
-    for (const auto& l : kLaunches)
-      if (match(l)) return true;
-  }
-  return false;
-}
 
 // relu-mask + CHW->NHWC transpose in one pass (backward of the fused
 // flatten): masked[n,p,q,c] = gout_chw[n,c,pq] * (out_chw > 0)
@@ -1212,18 +665,6 @@ __global__ void relu_mask_bwd_chw_kernel(const __bf16* __restrict__ gout,
   }
 }
 }  // namespace
-
-void relu_mask_bwd_chw(torch::Tensor gout2d, torch::Tensor out2d,
-                       torch::Tensor dst_nhwc, int64_t C, int64_t PQ) {
-  const int64_t N = gout2d.size(0);
-  const int64_t total = N * C * PQ;
-  int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
-  hipLaunchKernelGGL(relu_mask_bwd_chw_kernel, dim3(blocks), dim3(256), 0,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const __bf16*)gout2d.data_ptr(),
-                     (const __bf16*)out2d.data_ptr(),
-                     (__bf16*)dst_nhwc.data_ptr(), N, (int)C, (int)PQ);
-}
 
 // ===========================================================================
 // Fused Linear(+bias)+ReLU forward for the MLP trunk head (round 2):
@@ -1334,24 +775,6 @@ __global__ __launch_bounds__(256) void linear_relu_kernel(
   }
 }
 }  // namespace
-
-bool linear_relu_supported(int64_t K, int64_t N) {
-  return (K == 3136 && N == 1024);
-}
-
-void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
-                 torch::Tensor out) {
-  const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
-  TORCH_CHECK(linear_relu_supported(K, N), "no linear_relu instantiation");
-  const __bf16* bp =
-      (b.defined() && b.numel()) ? (const __bf16*)b.data_ptr() : nullptr;
-  dim3 grid((M + 31) / 32, N / 256);
-  hipLaunchKernelGGL((linear_relu_kernel<3136, 1024, 256>), grid, dim3(256),
-                     0, (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const __bf16*)x.data_ptr(), (const __bf16*)w.data_ptr(),
-                     bp, (__bf16*)out.data_ptr(), M);
-}
 
 // ===========================================================================
 // 3x3 stride-1 pad-1 forward for the IMPALA-ResNet torso
@@ -1573,7 +996,470 @@ const Conv3Launch* find_conv3(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   return nullptr;
 }
 
+// ===========================================================================
+// Geometry table of the strided no-pad convs: ONE entry per
+// (H, W, C, KH, KW, S, COUT, u8) carries every kernel of that geometry, so
+// a new geometry or variant is one line here.
+// ===========================================================================
+
+// run-time twin of ConvGeom's template arguments
+struct Geom {
+  int64_t H, W, C, KH, KW, S, COUT;
+  bool u8;
+  int64_t P() const { return (H - KH) / S + 1; }
+  int64_t Q() const { return (W - KW) / S + 1; }
+  int64_t K() const { return KH * KW * C; }
+  bool operator==(const Geom& o) const {
+    return H == o.H && W == o.W && C == o.C && KH == o.KH && KW == o.KW &&
+           S == o.S && COUT == o.COUT && u8 == o.u8;
+  }
+};
+
+// the one matcher of every table whose entries start with a Geom g
+template <typename Entry, size_t N>
+const Entry* find_geom(const Entry (&table)[N], const Geom& g) {
+  for (const auto& e : table)
+    if (e.g == g) return &e;
+  return nullptr;
+}
+
+using FwdFn = void (*)(const void*, const __bf16*, const __bf16*, __bf16*, int);
+using GroupedFn = void (*)(const ConvJobs, int, int);
+
+struct ConvEntry {
+  Geom g;
+  // forwards; waves/rpw/lds_bytes are shared by all four (the CHW-out
+  // variants run the tile shape of their NHWC twins). Null: no such variant.
+  int waves, rpw, lds_bytes;
+  FwdFn fwd;
+  GroupedFn grouped;
+  FwdFn fwd_chw;
+  GroupedFn grouped_chw;
+  // weight-grad + its bias-grad column sum (null in the tuning table)
+  void (*wrw)(const void*, const __bf16*, float*, int, int);
+  int wrw_lds_bytes, ktiles;
+  void (*colsum)(const __bf16*, int64_t, float*);
+};
+
+enum : int { kGrouped = 1, kChw = 2, kChwGrouped = 4, kWrw = 8 };
+
+template <int H, int W, int C, int KH, int KW, int S, int COUT, bool U8,
+          int WAVES, int RPW, int FLAGS>
+ConvEntry make_conv() {
+  using G = ConvGeom<H, W, C, KH, KW, S, COUT, U8>;
+  // conv_wrw recovers KH/KW from the output extent
+  static_assert((H - KH) % S == 0 && (W - KW) % S == 0, "ragged last window");
+  ConvEntry e{};
+  e.g = Geom{H, W, C, KH, KW, S, COUT, U8};
+  e.waves = WAVES;
+  e.rpw = RPW;
+  e.lds_bytes = (int)(G::LDS_ELEMS * sizeof(__bf16));
+  e.fwd = conv_fwd_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW, false>;
+  if constexpr (FLAGS & kGrouped)
+    e.grouped =
+        conv_fwd_grouped_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW, false>;
+  if constexpr (FLAGS & kChw)
+    e.fwd_chw = conv_fwd_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW, true>;
+  if constexpr (FLAGS & kChwGrouped)
+    e.grouped_chw =
+        conv_fwd_grouped_kernel<H, W, C, KH, KW, S, COUT, U8, WAVES, RPW, true>;
+  if constexpr (FLAGS & kWrw) {
+    static_assert(G::K % 64 == 0, "wrw needs K % 64 == 0");
+    e.wrw = conv_wrw_kernel<H, W, C, KH, KW, S, COUT, U8>;
+    e.wrw_lds_bytes = (int)(32 * (64 + kPadM + COUT + kPadM) * sizeof(__bf16));
+    e.ktiles = G::K / 64;
+    e.colsum = colsum_bf16_kernel<COUT>;
+  }
+  return e;
+}
+
+static const ConvEntry kConvs[] = {
+    // Ape-X / R2D2 stack (cfg/ape_x.json:38-51); WAVES/RPW picked by the
+    // variant sweep in tools/gpu_conv_tune.py (profiles/). The last conv of a
+    // stack also has the CHW-out (flatten-fusing) forwards.
+    make_conv<84, 84, 4, 8, 8, 4, 32, true, 8, 32, kGrouped | kWrw>(),
+    make_conv<84, 84, 4, 8, 8, 4, 32, false, 8, 32, kGrouped | kWrw>(),
+    make_conv<20, 20, 32, 4, 4, 2, 64, false, 8, 16, kGrouped | kWrw>(),
+    make_conv<9, 9, 64, 3, 3, 1, 64, false, 8, 16,
+              kGrouped | kChw | kChwGrouped | kWrw>(),
+    // IMPALA stack (cfg/impala.json:26-39)
+    make_conv<84, 84, 4, 8, 8, 4, 16, true, 8, 16, kWrw>(),
+    make_conv<84, 84, 4, 8, 8, 4, 16, false, 8, 16, kWrw>(),
+    make_conv<20, 20, 16, 4, 4, 2, 32, false, 8, 16, kChw | kWrw>(),
+};
+
+// variant table for on-GPU tuning (tools/gpu_conv_tune.py): single-job NHWC
+// forward only
+static const ConvEntry kVariants[] = {
+    make_conv<84, 84, 4, 8, 8, 4, 32, true, 4, 16, 0>(),
+    make_conv<84, 84, 4, 8, 8, 4, 32, true, 8, 16, 0>(),
+    make_conv<84, 84, 4, 8, 8, 4, 32, true, 4, 32, 0>(),
+    make_conv<84, 84, 4, 8, 8, 4, 32, true, 8, 32, 0>(),
+    make_conv<20, 20, 32, 4, 4, 2, 64, false, 4, 16, 0>(),
+    make_conv<20, 20, 32, 4, 4, 2, 64, false, 8, 16, 0>(),
+    make_conv<20, 20, 32, 4, 4, 2, 64, false, 4, 32, 0>(),
+    make_conv<20, 20, 32, 4, 4, 2, 64, false, 8, 32, 0>(),
+    make_conv<9, 9, 64, 3, 3, 1, 64, false, 4, 16, 0>(),
+    make_conv<9, 9, 64, 3, 3, 1, 64, false, 8, 16, 0>(),
+    make_conv<9, 9, 64, 3, 3, 1, 64, false, 4, 32, 0>(),
+    make_conv<9, 9, 64, 3, 3, 1, 64, false, 8, 32, 0>(),
+};
+
+struct DgradEntry {
+  Geom g;  // u8 is always false: dgrad never meets the u8 first layer
+  void (*fn)(const __bf16*, const __bf16*, __bf16*, int);
+  int waves, rpw;
+};
+
+template <int H, int W, int C, int KH, int KW, int S, int COUT, int WAVES = 8,
+          int RPW = 16>
+DgradEntry make_dgrad() {
+  return DgradEntry{Geom{H, W, C, KH, KW, S, COUT, false},
+                    conv_dgrad_kernel<H, W, C, KH, KW, S, COUT, WAVES, RPW>,
+                    WAVES, RPW};
+}
+
+static const DgradEntry kDgrad[] = {
+    make_dgrad<20, 20, 32, 4, 4, 2, 64>(),  // apex/r2d2 conv2
+    make_dgrad<9, 9, 64, 3, 3, 1, 64>(),    // apex/r2d2 conv3
+    make_dgrad<20, 20, 16, 4, 4, 2, 32>(),  // impala conv2
+};
+
+const ConvEntry* find_conv(int64_t H, int64_t W, int64_t C, int64_t KH,
+                           int64_t KW, int64_t S, int64_t COUT, bool u8) {
+  return find_geom(kConvs, Geom{H, W, C, KH, KW, S, COUT, u8});
+}
+
+// ===========================================================================
+// Argument checks. Every tensor a kernel dereferences goes through one of
+// these before its pointer is taken: on the device, the expected dtype, and
+// exactly the sizes and memory layout the geometry implies — an
+// out-of-bounds launch takes the card down, not just the test.
+// ===========================================================================
+
+constexpr auto kBF16 = torch::kBFloat16;
+
+hipStream_t cur_stream() {
+  return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
+}
+
+void check_dev(const torch::Tensor& t, at::ScalarType dtype, const char* what) {
+  TORCH_CHECK(t.defined() && t.is_cuda(), what, " must be a device tensor");
+  TORCH_CHECK(t.scalar_type() == dtype, what, " must be ", dtype, ", got ",
+              t.scalar_type());
+}
+
+// plain contiguous tensor of exactly `sizes`
+void check_rows(const torch::Tensor& t, at::ScalarType dtype,
+                at::IntArrayRef sizes, const char* what) {
+  check_dev(t, dtype, what);
+  TORCH_CHECK(t.sizes() == sizes && t.is_contiguous(), what,
+              " must be contiguous ", sizes, ", got ", t.sizes());
+}
+
+// logical (n, c, h, w) tensor in channels_last (NHWC) memory
+void check_nhwc(const torch::Tensor& t, at::ScalarType dtype, int64_t n,
+                int64_t c, int64_t h, int64_t w, const char* what) {
+  check_dev(t, dtype, what);
+  TORCH_CHECK(t.sizes() == at::IntArrayRef({n, c, h, w}), what, " must be (",
+              n, ", ", c, ", ", h, ", ", w, "), got ", t.sizes());
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), what,
+              " must be channels_last");
+}
+
+// optional (n) bf16 vector: undefined or empty means "none"
+const __bf16* opt_vec(const torch::Tensor& t, int64_t n, const char* what) {
+  if (!t.defined() || t.numel() == 0) return nullptr;
+  check_rows(t, kBF16, {n}, what);
+  return (const __bf16*)t.data_ptr();
+}
+
+// kernels index rows with int
+int checked_rows(int64_t rows, const char* what) {
+  TORCH_CHECK(rows < (int64_t)1 << 31, what, ": too many rows");
+  return (int)rows;
+}
+
+// geometry of a forward call, from its first job
+Geom geom_of(const torch::Tensor& in, const torch::Tensor& weight,
+             int64_t stride) {
+  TORCH_CHECK(in.dim() == 4 && weight.dim() == 4 && stride >= 1,
+              "conv wants 4-D input and weight and a positive stride");
+  return Geom{in.size(2), in.size(3), in.size(1), weight.size(2),
+              weight.size(3), stride, weight.size(0),
+              in.scalar_type() == torch::kUInt8};
+}
+
+// The one forward launch path: checks every job against entry e, then runs
+// e's single-job kernel for one job (grid = row tiles) and its grouped kernel
+// for 2..kMaxConvJobs (grid = tiles * njobs). biases is empty (no job has a
+// bias) or one tensor per job.
+void launch_conv_fwd(const ConvEntry& e, const std::vector<torch::Tensor>& ins,
+                     const std::vector<torch::Tensor>& weights,
+                     const std::vector<torch::Tensor>& biases,
+                     const std::vector<torch::Tensor>& outs, bool chw_out) {
+  const Geom& g = e.g;
+  const int njobs = (int)ins.size();
+  const FwdFn single = chw_out ? e.fwd_chw : e.fwd;
+  const GroupedFn grouped = chw_out ? e.grouped_chw : e.grouped;
+  TORCH_CHECK(njobs > 1 ? grouped != nullptr : single != nullptr, "no ",
+              njobs > 1 ? "grouped" : "fused",
+              " conv kernel for this geometry: ", g.H, "x", g.W, "x", g.C,
+              " k", g.KH, "x", g.KW, " s", g.S, " -> ", g.COUT, " u8=", g.u8,
+              " chw=", chw_out);
+  const int64_t N = ins[0].size(0), P = g.P(), Q = g.Q();
+  const int M = checked_rows(N * P * Q, "conv_fwd");
+  ConvJobs jobs{};
+  for (int j = 0; j < njobs; ++j) {
+    check_nhwc(ins[j], g.u8 ? torch::kUInt8 : kBF16, N, g.C, g.H, g.W,
+               "conv input (jobs share N and geometry)");
+    check_nhwc(weights[j], kBF16, g.COUT, g.C, g.KH, g.KW, "conv weight");
+    if (chw_out)
+      check_rows(outs[j], kBF16, {N, g.COUT * P * Q}, "conv CHW output");
+    else
+      check_nhwc(outs[j], kBF16, N, g.COUT, P, Q, "conv output");
+    jobs.in[j] = ins[j].data_ptr();
+    jobs.weight[j] = (const __bf16*)weights[j].data_ptr();
+    jobs.out[j] = (__bf16*)outs[j].data_ptr();
+    jobs.bias[j] =
+        biases.empty() ? nullptr : opt_vec(biases[j], g.COUT, "conv bias");
+  }
+  if (M == 0) return;
+  const int rows_per_block = e.waves * e.rpw;
+  const int tiles = (M + rows_per_block - 1) / rows_per_block;
+  if (njobs == 1)
+    hipLaunchKernelGGL(single, dim3(tiles), dim3(e.waves * 64), e.lds_bytes,
+                       cur_stream(), jobs.in[0], jobs.weight[0], jobs.bias[0],
+                       jobs.out[0], (int)N);
+  else
+    hipLaunchKernelGGL(grouped, dim3(tiles * njobs), dim3(e.waves * 64),
+                       e.lds_bytes, cur_stream(), jobs, njobs, (int)N);
+}
+
 }  // namespace
+
+// ===========================================================================
+// Host entry points
+// ===========================================================================
+
+void mfma_probe(torch::Tensor A, torch::Tensor B, torch::Tensor C) {
+  hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0,
+                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
+                     (const __bf16*)A.data_ptr(), (const __bf16*)B.data_ptr(),
+                     C.data_ptr<float>());
+}
+
+void tr16_probe(torch::Tensor out, int64_t mode) {
+  hipLaunchKernelGGL(tr16_probe_kernel, dim3(1), dim3(64), 0,
+                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
+                     out.data_ptr<float>(), (int)mode);
+}
+
+// True when the geometry has a forward with the requested output form for
+// this many same-geometry jobs (more than one job needs a grouped variant).
+bool conv_fwd_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
+                        int64_t S, int64_t COUT, bool u8, bool chw_out,
+                        int64_t njobs) {
+  const ConvEntry* e = find_conv(H, W, C, KH, KW, S, COUT, u8);
+  if (!e || njobs < 1 || njobs > kMaxConvJobs) return false;
+  if (njobs > 1) return (chw_out ? e->grouped_chw : e->grouped) != nullptr;
+  return (chw_out ? e->fwd_chw : e->fwd) != nullptr;
+}
+
+// Fused conv + bias + ReLU forward for 1..kMaxConvJobs jobs of one geometry
+// and batch size in a single launch (see conv_fwd_grouped_kernel).
+// ins: (N,C,H,W) logical, channels_last, uint8 (dequant fused) or bf16;
+// weights: (COUT,C,KH,KW) logical channels_last bf16; biases: empty, or one
+// (COUT) bf16 tensor per job; outs: (N,COUT,P,Q) logical channels_last bf16,
+// or with chw_out the flatten-fused 2-D (N, COUT*P*Q) in logical-NCHW order.
+void conv_fwd_grouped(std::vector<torch::Tensor> ins,
+                      std::vector<torch::Tensor> weights,
+                      std::vector<torch::Tensor> biases,
+                      std::vector<torch::Tensor> outs, int64_t stride,
+                      bool chw_out) {
+  const size_t njobs = ins.size();
+  TORCH_CHECK(njobs >= 1 && njobs <= kMaxConvJobs, "1..", kMaxConvJobs,
+              " conv jobs per launch");
+  TORCH_CHECK(weights.size() == njobs && outs.size() == njobs &&
+                  (biases.empty() || biases.size() == njobs),
+              "conv_fwd_grouped wants one weight, output and bias per job");
+  const Geom g = geom_of(ins[0], weights[0], stride);
+  const ConvEntry* e = find_geom(kConvs, g);
+  TORCH_CHECK(e, "no fused conv kernel for this geometry: ", g.H, "x", g.W,
+              "x", g.C, " k", g.KH, "x", g.KW, " s", g.S, " -> ", g.COUT,
+              " u8=", g.u8);
+  launch_conv_fwd(*e, ins, weights, biases, outs, chw_out);
+}
+
+// Run a specific tuning variant (tools/gpu_conv_tune.py); returns false if
+// the variant index does not match the geometry.
+bool conv_fwd_variant(torch::Tensor in, torch::Tensor weight,
+                      torch::Tensor bias, torch::Tensor out, int64_t stride,
+                      int64_t variant) {
+  if (variant < 0 || variant >= (int64_t)std::size(kVariants)) return false;
+  const ConvEntry& e = kVariants[variant];
+  if (!(e.g == geom_of(in, weight, stride))) return false;
+  launch_conv_fwd(e, {in}, {weight}, {bias}, {out}, false);
+  return true;
+}
+
+bool conv_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
+                        int64_t S, int64_t COUT, bool u8) {
+  const ConvEntry* e = find_conv(H, W, C, KH, KW, S, COUT, u8);
+  return e && e->wrw;
+}
+
+// in: (N,C,H,W) channels_last u8/bf16; gout: (N,COUT,P,Q) channels_last bf16
+// (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 and gb_ws: (COUT) fp32
+// (or empty), both fully overwritten. bf16 gw_ws/gb_ws are the gradients
+// themselves: gw_ws then holds COUT*KH*KW*C elements in (cout, kh, kw, c)
+// memory order (a channels_last weight-shaped tensor or its flat view).
+void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
+              torch::Tensor gb_ws, int64_t stride) {
+  TORCH_CHECK(in.dim() == 4 && gout.dim() == 4 && stride >= 1,
+              "conv_wrw wants 4-D in and gout and a positive stride");
+  const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
+  const int64_t COUT = gout.size(1), P = gout.size(2), Q = gout.size(3);
+  const bool u8 = in.scalar_type() == torch::kUInt8;
+  // table geometries have no ragged last window (make_conv asserts it), so
+  // gout's extent fixes the kernel extent
+  const ConvEntry* L =
+      find_conv(H, W, C, H - (P - 1) * stride, W - (Q - 1) * stride, stride,
+                COUT, u8);
+  TORCH_CHECK(L && L->wrw, "no wrw kernel for this geometry");
+  check_nhwc(in, u8 ? torch::kUInt8 : kBF16, N, C, H, W, "conv_wrw in");
+  check_nhwc(gout, kBF16, N, COUT, P, Q, "conv_wrw gout (in's batch)");
+  const bool bf16_out = gw_ws.scalar_type() == kBF16;
+  check_dev(gw_ws, bf16_out ? kBF16 : torch::kFloat32, "conv_wrw gw_ws");
+  TORCH_CHECK(gw_ws.is_contiguous() ||
+              (gw_ws.dim() == 4 &&
+               gw_ws.is_contiguous(at::MemoryFormat::ChannelsLast)));
+  const int n_elem = (int)gw_ws.numel();
+  TORCH_CHECK(gw_ws.numel() == COUT * L->g.K(), "gw_ws shape mismatch");
+  const bool bias = gb_ws.defined() && gb_ws.numel() > 0;
+  if (bias) check_rows(gb_ws, gw_ws.scalar_type(), {COUT}, "conv_wrw gb_ws");
+  const int M = checked_rows(N * P * Q, "conv_wrw");
+  const int n_chunks = (M + 31) / 32;
+  // scale the m-grid with the batch: R2D2/IMPALA run 8-20x Ape-X's row
+  // count through the same kernel (conv1 wrw measured 139 us at 1.02M
+  // rows with 512 blocks = 250 serial chunks per block)
+  int mb = (n_chunks > 8192 ? 2048 : 512) / L->ktiles;  // every m-slice costs one partial plane of write + read traffic
+  if (mb > n_chunks) mb = n_chunks;
+  if (mb < 1) mb = 1;
+  auto st = cur_stream();
+  // per-m-slice partial planes (every (ktile, m-slice) block writes its
+  // whole 64 x COUT tile, so no zero-fill) + ordered reduction
+  const auto f32 = gw_ws.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)mb, (int64_t)n_elem + kPlanePad}, f32);
+  hipLaunchKernelGGL(L->wrw, dim3(L->ktiles, mb), dim3(256), L->wrw_lds_bytes,
+                     st, (const void*)in.data_ptr(),
+                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                     (int)N, mb);
+  constexpr int kColsumBlocks = 256;
+  torch::Tensor b_part;
+  if (bias) {
+    b_part = torch::empty({(int64_t)kColsumBlocks, COUT}, f32);
+    hipLaunchKernelGGL(L->colsum, dim3(kColsumBlocks), dim3(256), 0, st,
+                       (const __bf16*)gout.data_ptr(), (int64_t)M,
+                       b_part.data_ptr<float>());
+  }
+  const int e_blocks = (n_elem + 63) / 64;
+  const float* b_part_ptr =
+      bias ? (const float*)b_part.data_ptr<float>() : nullptr;
+  if (bf16_out)
+    hipLaunchKernelGGL(wrw_reduce_kernel<__bf16>,
+                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), mb, n_elem,
+                       (__bf16*)gw_ws.data_ptr(), b_part_ptr, kColsumBlocks,
+                       (int)COUT, bias ? (__bf16*)gb_ws.data_ptr() : nullptr);
+  else
+    hipLaunchKernelGGL(wrw_reduce_kernel<float>,
+                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), mb, n_elem,
+                       gw_ws.data_ptr<float>(), b_part_ptr, kColsumBlocks,
+                       (int)COUT, bias ? gb_ws.data_ptr<float>() : nullptr);
+}
+
+bool conv_dgrad_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
+                          int64_t KW, int64_t S, int64_t COUT) {
+  return find_geom(kDgrad, Geom{H, W, C, KH, KW, S, COUT, false}) != nullptr;
+}
+
+// gout: (N,COUT,P,Q) logical channels_last bf16; weight (COUT,C,KH,KW)
+// logical channels_last bf16; dx out (N,C,H,W) logical channels_last bf16;
+// w_t workspace (C*KH*KW*COUT) bf16.
+void conv_dgrad(torch::Tensor gout, torch::Tensor weight, torch::Tensor w_t,
+                torch::Tensor dx, int64_t stride) {
+  TORCH_CHECK(dx.dim() == 4 && weight.dim() == 4 && stride >= 1,
+              "conv_dgrad wants 4-D dx and weight and a positive stride");
+  const int64_t N = dx.size(0), C = dx.size(1), H = dx.size(2), W = dx.size(3);
+  const int64_t COUT = weight.size(0), KH = weight.size(2), KW = weight.size(3);
+  const DgradEntry* L =
+      find_geom(kDgrad, Geom{H, W, C, KH, KW, stride, COUT, false});
+  TORCH_CHECK(L, "no dgrad kernel for this geometry");
+  check_nhwc(dx, kBF16, N, C, H, W, "conv_dgrad dx");
+  check_nhwc(weight, kBF16, COUT, C, KH, KW, "conv_dgrad weight");
+  check_nhwc(gout, kBF16, N, COUT, L->g.P(), L->g.Q(), "conv_dgrad gout");
+  check_rows(w_t, kBF16, {weight.numel()}, "conv_dgrad w_t");
+  const int M = checked_rows(N * H * W, "conv_dgrad");
+  if (M == 0) return;
+  auto stream = cur_stream();
+  const int total = (int)weight.numel();
+  hipLaunchKernelGGL(conv_w_transpose_kernel, dim3((total + 255) / 256),
+                     dim3(256), 0, stream, (const __bf16*)weight.data_ptr(),
+                     (__bf16*)w_t.data_ptr(), (int)(KH * KW), (int)C,
+                     (int)COUT);
+  const int rows_per_block = L->waves * L->rpw;
+  const int blocks = (M + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), 0, stream,
+                     (const __bf16*)gout.data_ptr(),
+                     (const __bf16*)w_t.data_ptr(), (__bf16*)dx.data_ptr(),
+                     (int)N);
+}
+
+// backward of the flatten-fused forward: gout2d / out2d are the (N, C*PQ)
+// CHW-ordered grad and forward output, dst_nhwc the (N,C,P,Q) logical
+// channels_last relu-masked grad.
+void relu_mask_bwd_chw(torch::Tensor gout2d, torch::Tensor out2d,
+                       torch::Tensor dst_nhwc, int64_t C, int64_t PQ) {
+  TORCH_CHECK(gout2d.dim() == 2 && dst_nhwc.dim() == 4 && C >= 1 && PQ >= 1);
+  const int64_t N = gout2d.size(0);
+  check_rows(gout2d, kBF16, {N, C * PQ}, "relu_mask_bwd_chw gout");
+  check_rows(out2d, kBF16, {N, C * PQ}, "relu_mask_bwd_chw out");
+  TORCH_CHECK(dst_nhwc.size(2) * dst_nhwc.size(3) == PQ,
+              "relu_mask_bwd_chw dst must have P*Q == ", PQ);
+  check_nhwc(dst_nhwc, kBF16, N, C, dst_nhwc.size(2), dst_nhwc.size(3),
+             "relu_mask_bwd_chw dst");
+  const int64_t total = N * C * PQ;
+  if (total == 0) return;
+  int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
+  hipLaunchKernelGGL(relu_mask_bwd_chw_kernel, dim3(blocks), dim3(256), 0,
+                     cur_stream(), (const __bf16*)gout2d.data_ptr(),
+                     (const __bf16*)out2d.data_ptr(),
+                     (__bf16*)dst_nhwc.data_ptr(), N, (int)C, (int)PQ);
+}
+
+bool linear_relu_supported(int64_t K, int64_t N) {
+  return (K == 3136 && N == 1024);
+}
+
+// out(M, N) = relu(x(M, K) @ w(N, K)^T + b(N)), all bf16; b may be empty.
+void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
+                 torch::Tensor out) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2);
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(linear_relu_supported(K, N), "no linear_relu instantiation");
+  check_rows(x, kBF16, {M, K}, "linear_relu x");
+  check_rows(w, kBF16, {N, K}, "linear_relu w");
+  check_rows(out, kBF16, {M, N}, "linear_relu out");
+  const __bf16* bp = opt_vec(b, N, "linear_relu bias");
+  if (M == 0) return;
+  dim3 grid((checked_rows(M, "linear_relu") + 31) / 32, N / 256);
+  hipLaunchKernelGGL((linear_relu_kernel<3136, 1024, 256>), grid, dim3(256),
+                     0, cur_stream(), (const __bf16*)x.data_ptr(),
+                     (const __bf16*)w.data_ptr(), bp, (__bf16*)out.data_ptr(),
+                     (int)M);
+}
 
 bool conv3x3p1_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   return find_conv3(H, W, C, COUT) != nullptr;
@@ -1586,22 +1472,12 @@ bool conv3x3p1_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
 void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
                    torch::Tensor residual, torch::Tensor out, bool relu_in,
                    bool relu_out) {
-  TORCH_CHECK(in.is_cuda() && weight.is_cuda() && out.is_cuda());
-  TORCH_CHECK(in.dim() == 4 && weight.dim() == 4 && out.dim() == 4);
-  TORCH_CHECK(in.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3p1_fwd input must be channels_last");
-  TORCH_CHECK(out.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(weight.is_contiguous(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(in.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(weight.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(in.dim() == 4 && weight.dim() == 4);
   const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
   const int64_t COUT = weight.size(0);
-  TORCH_CHECK(weight.size(1) == C && weight.size(2) == 3 && weight.size(3) == 3,
-              "conv3x3p1_fwd weight must be (COUT, C, 3, 3)");
-  TORCH_CHECK(out.size(0) == N && out.size(1) == COUT && out.size(2) == H &&
-                  out.size(3) == W,
-              "conv3x3p1_fwd output shape mismatch");
+  check_nhwc(in, kBF16, N, C, H, W, "conv3x3p1_fwd input");
+  check_nhwc(weight, kBF16, COUT, C, 3, 3, "conv3x3p1_fwd weight");
+  check_nhwc(out, kBF16, N, COUT, H, W, "conv3x3p1_fwd output");
   TORCH_CHECK(out.data_ptr() != in.data_ptr(), "conv3x3p1_fwd is not in-place");
   // 16-byte pieces of in / weight, 8-byte pieces of out / residual
   TORCH_CHECK((uintptr_t)in.data_ptr() % 16 == 0 &&
@@ -1611,32 +1487,47 @@ void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
   const Conv3Launch* L = find_conv3(H, W, C, COUT);
   TORCH_CHECK(L, "no 3x3 pad-1 conv kernel for this geometry: ", H, "x", W, "x",
               C, " -> ", COUT);
-  TORCH_CHECK(N * H * W < (int64_t)1 << 31, "conv3x3p1_fwd: too many rows");
-  const __bf16* bias_ptr = nullptr;
-  if (bias.defined() && bias.numel() > 0) {
-    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == torch::kBFloat16 &&
-                bias.numel() == COUT && bias.is_contiguous());
-    bias_ptr = (const __bf16*)bias.data_ptr();
-  }
+  const int M = checked_rows(N * H * W, "conv3x3p1_fwd");
+  const __bf16* bias_ptr = opt_vec(bias, COUT, "conv3x3p1_fwd bias");
   const __bf16* res_ptr = nullptr;
   if (residual.defined() && residual.numel() > 0) {
-    TORCH_CHECK(residual.is_cuda() &&
-                residual.scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(residual.sizes() == out.sizes(),
-                "conv3x3p1_fwd residual must have the output's shape");
-    TORCH_CHECK(residual.is_contiguous(at::MemoryFormat::ChannelsLast));
+    check_nhwc(residual, kBF16, N, COUT, H, W, "conv3x3p1_fwd residual");
     TORCH_CHECK((uintptr_t)residual.data_ptr() % 8 == 0,
                 "conv3x3p1_fwd: misaligned residual");
     res_ptr = (const __bf16*)residual.data_ptr();
   }
   if (N == 0) return;
-  const int M = (int)(N * H * W);
   const int rows_per_block = L->waves * L->rpw;
   const int blocks = (M + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), L->lds_bytes,
-                     (hipStream_t)at::cuda::getCurrentCUDAStream().stream(),
-                     (const __bf16*)in.data_ptr(),
+                     cur_stream(), (const __bf16*)in.data_ptr(),
                      (const __bf16*)weight.data_ptr(), bias_ptr, res_ptr,
                      (__bf16*)out.data_ptr(), (int)N, relu_in ? 1 : 0,
                      relu_out ? 1 : 0);
+}
+
+void register_conv(pybind11::module_& m) {
+  m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA fragment-map probe");
+  m.def("tr16_probe", &tr16_probe);
+  m.def("conv_fwd_grouped", &conv_fwd_grouped,
+        "fused NHWC bf16 MFMA conv fwd (+dequant on u8 input, bias, ReLU, "
+        "optional flatten-fused CHW out) for 1..4 same-geometry jobs in one "
+        "launch");
+  m.def("conv_fwd_supported", &conv_fwd_supported);
+  m.def("conv_fwd_variant", &conv_fwd_variant, "tuning-variant conv fwd");
+  m.def("conv_wrw", &conv_wrw,
+        "MFMA conv weight-grad; gw/gb are fp32 workspaces or bf16 grads");
+  m.def("conv_wrw_supported", &conv_wrw_supported);
+  m.def("conv_dgrad", &conv_dgrad,
+        "MFMA conv data-grad (masked-tap gather, pre-transposed weights)");
+  m.def("conv_dgrad_supported", &conv_dgrad_supported);
+  m.def("relu_mask_bwd_chw", &relu_mask_bwd_chw,
+        "relu-mask + CHW->NHWC transpose (backward of the fused flatten)");
+  m.def("linear_relu", &linear_relu,
+        "fused Linear+bias+ReLU fwd (own MFMA GEMM, LDS-staged W)");
+  m.def("linear_relu_supported", &linear_relu_supported);
+  m.def("conv3x3p1_fwd", &conv3x3p1_fwd,
+        "MFMA 3x3 s1 pad-1 NHWC bf16 conv fwd (+relu_in, bias, residual, "
+        "relu_out)");
+  m.def("conv3x3p1_supported", &conv3x3p1_supported);
 }

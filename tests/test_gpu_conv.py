@@ -245,11 +245,16 @@ def test_conv_dgrad_in_fused_backward(ext, monkeypatch):
 
 def test_conv_chw_out_matches_flatten(ext):
     """CHW-out epilogue (flatten fused) must equal conv_fwd + torch.flatten,
-    forward and backward (mask+transpose kernel)."""
+    forward and backward (mask+transpose kernel), at both stack-final
+    geometries: Ape-X/R2D2 conv3 and IMPALA conv2."""
+    for geom in [(16, 64, 9, 9, 64, 3, 1), (16, 16, 20, 20, 32, 4, 2)]:
+        _check_chw_out_matches_flatten(*geom)
+
+
+def _check_chw_out_matches_flatten(N, C, H, W, COUT, KH, S):
     from distributed_rl_amd.ops import fused_conv_relu
 
     torch.manual_seed(9)
-    N, C, H, W, COUT, KH, S = 16, 64, 9, 9, 64, 3, 1
     x = (torch.randn(N, C, H, W, device=DEV) * 0.5).to(torch.bfloat16
         ).contiguous(memory_format=torch.channels_last).requires_grad_(True)
     x2 = x.detach().clone().requires_grad_(True)

@@ -1,6 +1,7 @@
 """On-GPU sweep of conv-kernel variants (WAVES, RPW) vs MIOpen.
 
-Writes timings to stdout; pick winners into kLaunches (conv_mfma.hip)."""
+Writes timings to stdout; pick winners into kConvs (conv_mfma.hip). The
+variant indices below are positions in that file's kVariants table."""
 
 import os
 import sys
