@@ -291,7 +291,7 @@ def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
 
 # ---------------------------------------------------------------------------
 # K2b — fused MFMA 3x3 stride-1 pad-1 conv for the IMPALA-ResNet torso
-# (relu_in / bias / residual / relu_out fused; aten backward)
+# (relu_in / bias / residual / relu_out fused; own wrw + dgrad backward)
 # ---------------------------------------------------------------------------
 
 
@@ -300,7 +300,30 @@ def conv3x3_supported(H, W, C, COUT) -> bool:
     return ext is not None and bool(ext.conv3x3p1_supported(H, W, C, COUT))
 
 
+def _gate(name: str, default: bool) -> bool:
+    """Read at call time: '1' forces the own kernel, '0' the library; unset
+    takes the measured default."""
+    v = os.environ.get(name)
+    if v is None or v == "":
+        return default
+    return v == "1"
+
+
+# defaults of DRL_OWN_RESCONV_WRW / DRL_OWN_RESCONV_DGRAD, decided by the A/B
+# in profiles/r06_resconv_bwd.md: medians 5.948 (wrw only), 6.129 (dgrad
+# only), 5.550 (both) vs 6.503 ms/step for the parent, repeat spread at most
+# 0.014 ms -> both on
+_RESCONV_WRW_DEFAULT = True
+_RESCONV_DGRAD_DEFAULT = True
+
+
 class _FusedConv3x3Fn(torch.autograd.Function):
+    """Forward on conv3x3p1_fwd_kernel. Backward: the relu_out mask of gout
+    as one relu_mask_bwd pass, then the own weight gradient
+    (conv3x3p1_wrw, gate DRL_OWN_RESCONV_WRW) and the own input gradient
+    (conv3x3p1_dgrad, gate DRL_OWN_RESCONV_DGRAD); aten.convolution_backward
+    runs only what a closed gate or an unsupported geometry leaves over."""
+
     @staticmethod
     def forward(ctx, x, weight, bias, residual, relu_in, relu_out):
         ext = hip_ext()
@@ -336,22 +359,56 @@ class _FusedConv3x3Fn(torch.autograd.Function):
         need_w = ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         gres = gout if ctx.needs_input_grad[3] else None
+        C, H, W = x.shape[1], x.shape[2], x.shape[3]
+        own_wrw = need_w and _gate("DRL_OWN_RESCONV_WRW", _RESCONV_WRW_DEFAULT) \
+            and bool(ext.conv3x3p1_wrw_supported(H, W, C, COUT))
+        # the input gradient is the forward kernel at the mirrored geometry
+        own_dgrad = need_x \
+            and _gate("DRL_OWN_RESCONV_DGRAD", _RESCONV_DGRAD_DEFAULT) \
+            and bool(ext.conv3x3p1_supported(H, W, COUT, C))
         gx = gw = gb = None
-        if need_x or need_w or need_b:
-            # weight- and input-gradient kernels for the padded geometries
-            # are the follow-up: the library runs them
-            gx, gw, gb = torch.ops.aten.convolution_backward(
-                gout, torch.relu(x) if ctx.relu_in else x, weight,
-                [COUT] if ctx.has_bias else None,
-                [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                [need_x, need_w, need_b],
+        if own_wrw:
+            # ordered partial planes (reproducible); relu_in is applied as x
+            # is staged, and the fold writes the bf16 grads directly:
+            # (COUT, 9C) in (kh, kw, c) order is the channels_last layout
+            gw = torch.empty(COUT, 3, 3, C, dtype=torch.bfloat16,
+                             device=x.device).permute(0, 3, 1, 2)
+            gb = (torch.empty(COUT, dtype=torch.bfloat16, device=x.device)
+                  if need_b else None)
+            ext.conv3x3p1_wrw(x, gout, gw,
+                              gb if need_b else torch.empty(0, device=x.device),
+                              ctx.relu_in)
+        if own_dgrad:
+            # weight flip + forward kernel; the relu_in mask rides in the
+            # epilogue instead of a relu_mask_bwd pass
+            gx = torch.empty_like(x)
+            w_flip = torch.empty(weight.numel(), dtype=torch.bfloat16,
+                                 device=x.device)
+            ext.conv3x3p1_dgrad(
+                gout, weight, w_flip, gx,
+                x if ctx.relu_in else torch.empty(0, device=x.device,
+                                                  dtype=torch.bfloat16))
+        lib = [need_x and not own_dgrad, need_w and not own_wrw,
+               need_b and not own_wrw]
+        if any(lib):
+            # what a closed gate or an unsupported geometry leaves over
+            gx2, gw2, gb2 = torch.ops.aten.convolution_backward(
+                gout, torch.relu(x) if ctx.relu_in and lib[1] else x,
+                weight, [COUT] if ctx.has_bias else None,
+                [1, 1], [1, 1], [1, 1], False, [0, 0], 1, lib,
             )
-            if need_x and ctx.relu_in:
-                if not gx.is_contiguous(memory_format=torch.channels_last):
-                    gx = gx.contiguous(memory_format=torch.channels_last)
-                masked = torch.empty_like(gx)
-                ext.relu_mask_bwd(gx, x, masked)
-                gx = masked
+            if lib[0]:
+                gx = gx2
+                if ctx.relu_in:
+                    if not gx.is_contiguous(memory_format=torch.channels_last):
+                        gx = gx.contiguous(memory_format=torch.channels_last)
+                    masked = torch.empty_like(gx)
+                    ext.relu_mask_bwd(gx, x, masked)
+                    gx = masked
+            if lib[1]:
+                gw = gw2
+            if lib[2]:
+                gb = gb2
         return (gx if need_x else None), gw, gb, gres, None, None
 
 

@@ -23,6 +23,7 @@
 //   C/D: lane l holds C[row=(l>>4)*4 + r][col=l&15], r=0..3
 
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -794,6 +795,10 @@ __global__ __launch_bounds__(256) void linear_relu_kernel(
 //     output row per lane -> 8-byte residual loads and output stores.
 //   * fusions: relu_in on the A pieces as they are loaded; epilogue in f32:
 //     + bias, + residual, ReLU (relu_out), round to bf16.
+//   * MASK (compile-time; the input-gradient use below): the epilogue keeps
+//     v where mask > 0 and writes 0 elsewhere, decided on the f32 value
+//     before rounding — the relu_in mask of the conv whose input gradient
+//     this is. mask has the output's shape. MASK=false is the forward.
 // ===========================================================================
 namespace {
 
@@ -819,12 +824,13 @@ struct Conv3Geom {
   static_assert(COUT <= 64, "bias staging uses the first COUT threads");
 };
 
-template <int H, int W, int C, int COUT, int WAVES, int RPW>
+template <int H, int W, int C, int COUT, int WAVES, int RPW, bool MASK = false>
 __global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
     const __bf16* __restrict__ in,        // (N,H,W,C) NHWC
     const __bf16* __restrict__ weight,    // (COUT, 9C) = (cout, kh, kw, c)
     const __bf16* __restrict__ bias,      // (COUT), may be null
     const __bf16* __restrict__ residual,  // (N,H,W,COUT), may be null
+    const __bf16* __restrict__ mask,      // (N,H,W,COUT), MASK only
     __bf16* __restrict__ out,             // (N,H,W,COUT)
     int batch, int relu_in, int relu_out) {
   using G = Conv3Geom<C, COUT>;
@@ -919,6 +925,24 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
     }
   }
 
+  // the mask goes in flight with them too (bf16 bits: > 0 <=> sign clear
+  // and not zero, as relu_mask_bwd decides it)
+  using u16x4 = __attribute__((ext_vector_type(4))) unsigned short;
+  u16x4 mv[MASK ? RFRAG : 1][MASK ? NFRAG : 1];
+  if constexpr (MASK) {
+#pragma unroll
+    for (int rf = 0; rf < RFRAG; ++rf) {
+      const int orow = row0 + rf * 16 + (lane & 15);
+#pragma unroll
+      for (int f = 0; f < NFRAG; ++f) {
+        mv[rf][f] = u16x4{};
+        if (orow < M)
+          mv[rf][f] = *reinterpret_cast<const u16x4*>(
+              mask + (int64_t)orow * COUT + f * 16 + ccol);
+      }
+    }
+  }
+
   // ---- phase 2: relu_in on the bf16 bits (clear every element whose sign
   // bit is set), then the MFMAs
 #pragma unroll
@@ -957,6 +981,10 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
         float v = acc[rf][f][r] + (float)bv[r];
         v += (float)rv[rf][f][r];
         if (relu_out) v = v > 0.0f ? v : 0.0f;
+        if constexpr (MASK) {
+          const unsigned short mb = mv[rf][f][r];
+          if ((mb & 0x8000) || mb == 0) v = 0.0f;
+        }
         ov[r] = (__bf16)v;
       }
       *reinterpret_cast<bf16x4*>(out + (int64_t)orow * COUT + f * 16 + ccol) =
@@ -965,29 +993,256 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
   }
 }
 
-struct Conv3Launch {
-  int H, W, C, COUT;
-  void (*fn)(const __bf16*, const __bf16*, const __bf16*, const __bf16*,
-             __bf16*, int, int, int);
-  int lds_bytes;
-  int waves, rpw;
+// ---------------------------------------------------------------------------
+// Weight gradient of the same convs:
+//   gw[co][(kh,kw,c)] = sum_m gout[m][co] * im2col(x)[m][(kh,kw,c)], M = N*H*W
+// with K in the channels_last weight order, so no relayout follows. Built on
+// conv_wrw_kernel's scheme: 32-sample chunks staged plain row-major in LDS,
+// tr_frag fragments, fp32 MFMA accumulate, one fp32 plane per m-slice folded
+// in a fixed order by wrw_reduce_kernel (no float atomics: two calls on the
+// same inputs are bit-identical). What differs:
+//   * one block covers ALL of K (144 or 288 = 9 or 18 column blocks of 16),
+//     so the gout chunk is staged once per chunk, not once per K-tile; the
+//     staged x tile is [32][K+8] per chunk (< 19 KB). Wave w owns column blocks
+//     w, w+4, ... (3/2/2/2 of 9, 5/5/4/4 of 18) against every cout block.
+//   * padding as in the forward: an 8-element piece lies inside one tap and
+//     is live iff its tap is inside the image; dead pieces and rows past M
+//     stay zeros and their address is never formed into a load.
+//   * relu_in clears the sign-bit elements of the x pieces as they are
+//     staged (the forward's bit trick).
+//   * a block takes R consecutive 32-sample chunks per pass and loads the
+//     next pass's pieces into registers before the current pass's MFMAs.
+//     More chunks per pass put more bytes in flight but cost registers and
+//     LDS, i.e. resident blocks; R is picked per geometry from a
+//     measurement (profiles/r06_resconv_bwd.md).
+// Staging: thread t stages rows (t>>3) + 32s, pieces (t&7) + 8i of each —
+// the (n, p, q) decode is once per row, and eight neighbouring lanes read
+// 128 contiguous bytes.
+// ---------------------------------------------------------------------------
+template <int C, int COUT, int R>
+struct Conv3Wrw {
+  static constexpr int K = 9 * C;
+  static constexpr int NCB = K / 16;         // column blocks: 9 / 18
+  static constexpr int CBW = (NCB + 3) / 4;  // per wave: 3 / 5
+  static constexpr int CBLK = COUT / 16;
+  static constexpr int PPR = K / 8;          // x pieces per row: 18 / 36
+  static constexpr int XIT = (PPR + 7) / 8;  // staging passes: 3 / 5
+  static constexpr int GP = COUT / 8;        // gout pieces per row
+  static constexpr int XSTRIDE = K + kPadM;
+  static constexpr int GSTRIDE = COUT + kPadM;
+  static constexpr int ROWS = 32 * R;        // sample rows per pass
+  static constexpr int GIT = (ROWS * GP + 255) / 256;  // gout staging passes
+  static constexpr int LDS_BYTES = ROWS * (XSTRIDE + GSTRIDE) * 2;
+  static_assert(C % 8 == 0 && COUT % 16 == 0 && K % 16 == 0, "tiling");
+  static_assert(LDS_BYTES <= 64 * 1024, "dynamic LDS limit");
+  static_assert(XSTRIDE % 8 == 0 && GSTRIDE % 8 == 0, "16-byte LDS rows");
 };
 
-template <int H, int W, int C, int COUT, int WAVES, int RPW>
+template <int H, int W, int C, int COUT, int R>
+__global__ __launch_bounds__(256) void conv3x3p1_wrw_kernel(
+    const __bf16* __restrict__ x,     // (N,H,W,C) NHWC
+    const __bf16* __restrict__ gout,  // (M, COUT) = NHWC grad (relu-masked)
+    float* __restrict__ gw_part,      // (mblocks, COUT*K + kPlanePad) fp32
+    int batch, int mblocks, int relu_in) {
+  using G = Conv3Wrw<C, COUT, R>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* x_t = reinterpret_cast<__bf16*>(smem);  // [ROWS][XSTRIDE]
+  __bf16* g_t = x_t + G::ROWS * G::XSTRIDE;       // [ROWS][GSTRIDE]
+
+  const int mb = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  // wave-uniform in an SGPR: the column-block guards below must stay scalar
+  // branches (tr16 reads need the whole wave active)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int M = batch * H * W;
+  const int n_pass = (M + G::ROWS - 1) / G::ROWS;
+
+  f32x4 acc[G::CBW][G::CBLK];
+#pragma unroll
+  for (int i = 0; i < G::CBW; ++i)
+#pragma unroll
+    for (int cb = 0; cb < G::CBLK; ++cb) acc[i][cb] = {0.f, 0.f, 0.f, 0.f};
+
+  const int srow = tid >> 3;  // staged sample row 0..31 (+ 32s)
+  const int sj = tid & 7;     // first x piece of that row
+  const short relu_bits = relu_in ? (short)-1 : (short)0;
+
+  s16x8 xr[R][G::XIT];
+  s16x8 gr[G::GIT];
+  auto load_pass = [&](int mc) __attribute__((always_inline)) {
+    const int m0 = mc * G::ROWS;
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      const int m = m0 + s * 32 + srow;
+      const bool valid = m < M;
+      const int mcl = valid ? m : 0;
+      const int rem = mcl % (H * W);
+      const int p = rem / W;
+      const int q = rem - p * W;
+      const __bf16* xrow = x + (int64_t)mcl * C;  // ((n*H + p)*W + q)*C
+#pragma unroll
+      for (int i = 0; i < G::XIT; ++i) {
+        xr[s][i] = s16x8{};
+        const int kp = sj + 8 * i;
+        const int kelem = kp * 8;
+        const int tap = kelem / C;
+        const int c0 = kelem - tap * C;
+        const int th = tap / 3;
+        const int dy = th - 1;
+        const int dx = tap - th * 3 - 1;
+        const bool live = valid && kp < G::PPR &&
+                          (unsigned)(p + dy) < (unsigned)H &&
+                          (unsigned)(q + dx) < (unsigned)W;
+        if (live)
+          xr[s][i] = *reinterpret_cast<const s16x8*>(
+              xrow + (int64_t)(dy * W + dx) * C + c0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < G::GIT; ++t) {
+      const int piece = tid + 256 * t;
+      const int m = m0 + piece / G::GP;
+      gr[t] = s16x8{};
+      if (piece < G::ROWS * G::GP && m < M)
+        gr[t] = *reinterpret_cast<const s16x8*>(
+            gout + (int64_t)m * COUT + (piece % G::GP) * 8);
+    }
+  };
+
+  if (mb < n_pass) load_pass(mb);
+  for (int mc = mb; mc < n_pass; mc += mblocks) {
+    // ---- registers -> LDS (relu_in on the bf16 bits)
+#pragma unroll
+    for (int s = 0; s < R; ++s)
+#pragma unroll
+      for (int i = 0; i < G::XIT; ++i) {
+        const int kp = sj + 8 * i;
+        if (kp < G::PPR) {
+          const s16x8 v = xr[s][i];
+          *reinterpret_cast<s16x8*>(x_t + (s * 32 + srow) * G::XSTRIDE +
+                                    kp * 8) = v & ~((v >> 15) & relu_bits);
+        }
+      }
+#pragma unroll
+    for (int t = 0; t < G::GIT; ++t) {
+      const int piece = tid + 256 * t;
+      if (piece < G::ROWS * G::GP)
+        *reinterpret_cast<s16x8*>(g_t + (piece / G::GP) * G::GSTRIDE +
+                                  (piece % G::GP) * 8) = gr[t];
+    }
+    __syncthreads();
+    if (mc + mblocks < n_pass) load_pass(mc + mblocks);
+    // ---- fragments via tr16 reads + MFMA, chunk by chunk
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      bf16x8 gf[G::CBLK];
+#pragma unroll
+      for (int cb = 0; cb < G::CBLK; ++cb)
+        gf[cb] = tr_frag<G::GSTRIDE>(g_t + s * 32 * G::GSTRIDE, lane, cb);
+#pragma unroll
+      for (int i = 0; i < G::CBW; ++i) {
+        const int colblk = wave + 4 * i;
+        if (colblk < G::NCB) {
+          const bf16x8 xf =
+              tr_frag<G::XSTRIDE>(x_t + s * 32 * G::XSTRIDE, lane, colblk);
+#pragma unroll
+          for (int cb = 0; cb < G::CBLK; ++cb)
+            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                gf[cb], xf, acc[i][cb], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogue: this m-slice's partial goes to its own (COUT, K) plane
+  float* plane = gw_part + (int64_t)mb * (COUT * G::K + kPlanePad);
+#pragma unroll
+  for (int i = 0; i < G::CBW; ++i) {
+    const int colblk = wave + 4 * i;
+    if (colblk < G::NCB) {
+      const int kout = colblk * 16 + (lane & 15);
+#pragma unroll
+      for (int cb = 0; cb < G::CBLK; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int cout = cb * 16 + (lane >> 4) * 4 + r;
+          plane[cout * G::K + kout] = acc[i][cb][r];
+        }
+    }
+  }
+}
+
+// Input gradient: for a 3x3 stride-1 pad-1 conv it is itself a 3x3 stride-1
+// pad-1 conv of gout with the weight transposed and flipped,
+//   W'[ci][kh][kw][co] = W[co][2-kh][2-kw][ci],
+// so conv3x3p1_fwd_kernel runs it at the mirrored geometry (H, W, COUT, C).
+// One launch per conv writes W' (a kernel, not torch ops: the step is
+// graph-captured). Tap index t = kh*3 + kw flips to 8 - t.
+__global__ void conv3x3_w_flip_kernel(const __bf16* __restrict__ w,
+                                      __bf16* __restrict__ w_f, int C,
+                                      int COUT) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 9 * C * COUT) return;
+  const int ci = i / (9 * COUT);
+  const int rem = i - ci * (9 * COUT);
+  const int tap = rem / COUT;
+  const int co = rem - tap * COUT;
+  w_f[i] = w[(co * 9 + (8 - tap)) * C + ci];
+}
+
+using Conv3Fn = void (*)(const __bf16*, const __bf16*, const __bf16*,
+                         const __bf16*, const __bf16*, __bf16*, int, int, int);
+
+// ONE entry per (H, W, C, COUT) carries every kernel of that geometry
+struct Conv3Launch {
+  int H, W, C, COUT;
+  Conv3Fn fn;       // forward
+  Conv3Fn fn_mask;  // forward with the masked epilogue (input gradients)
+  int lds_bytes;
+  int waves, rpw;
+  // weight-grad + its bias-grad column sum (null: forward-only geometry)
+  void (*wrw)(const __bf16*, const __bf16*, float*, int, int, int);
+  int wrw_lds_bytes, wrw_rows;  // rows: samples a block takes per pass
+  void (*colsum)(const __bf16*, int64_t, float*);
+};
+
+// WRW_R: 32-sample chunks per pass of the weight-grad (0: forward only)
+template <int H, int W, int C, int COUT, int WAVES, int RPW, int WRW_R>
 Conv3Launch make_conv3() {
   using G = Conv3Geom<C, COUT>;
-  return Conv3Launch{H, W, C, COUT,
-                     conv3x3p1_fwd_kernel<H, W, C, COUT, WAVES, RPW>,
-                     G::LDS_BYTES, WAVES, RPW};
+  Conv3Launch l{};
+  l.H = H; l.W = W; l.C = C; l.COUT = COUT;
+  l.fn = conv3x3p1_fwd_kernel<H, W, C, COUT, WAVES, RPW, false>;
+  // every geometry has its masked twin, because conv3x3p1_dgrad takes a
+  // mask at every geometry; the model launches three of the five (the
+  // relu_in convs are the C -> C ones; 42x42x16->32 and 42x42x32->16 run
+  // masked only from the tests)
+  l.fn_mask = conv3x3p1_fwd_kernel<H, W, C, COUT, WAVES, RPW, true>;
+  l.lds_bytes = G::LDS_BYTES;
+  l.waves = WAVES;
+  l.rpw = RPW;
+  if constexpr (WRW_R > 0) {
+    l.wrw = conv3x3p1_wrw_kernel<H, W, C, COUT, WRW_R>;
+    l.wrw_lds_bytes = Conv3Wrw<C, COUT, WRW_R>::LDS_BYTES;
+    l.wrw_rows = 32 * WRW_R;
+    l.colsum = colsum_bf16_kernel<COUT>;
+  }
+  return l;
 }
 
 // cfg/impala_resnet.json at 84x84 (the first conv, C=4 -> K=36, stays on
 // the library)
 static const Conv3Launch kConv3Launches[] = {
-    make_conv3<42, 42, 16, 16, 8, 32>(),  // section-1 residual convs
-    make_conv3<42, 42, 16, 32, 8, 32>(),  // section-2 entry conv
-    make_conv3<21, 21, 32, 32, 8, 32>(),  // section-3 entry, sec-2 residual
-    make_conv3<11, 11, 32, 32, 8, 16>(),  // section-3 residual convs
+    // WRW_R: the fastest of 1, 2, 4 per geometry at 1344 images
+    // (profiles/r06_resconv_bwd.md)
+    make_conv3<42, 42, 16, 16, 8, 32, 1>(),  // section-1 residual convs
+    make_conv3<42, 42, 16, 32, 8, 32, 4>(),  // section-2 entry conv
+    make_conv3<21, 21, 32, 32, 8, 32, 2>(),  // section-3 entry, sec-2 residual
+    make_conv3<11, 11, 32, 32, 8, 16, 1>(),  // section-3 residual convs
+    // input gradient of the section-2 entry conv (forward kernels only)
+    make_conv3<42, 42, 32, 16, 8, 32, 0>(),
 };
 
 const Conv3Launch* find_conv3(int64_t H, int64_t W, int64_t C, int64_t COUT) {
@@ -1236,6 +1491,124 @@ void launch_conv_fwd(const ConvEntry& e, const std::vector<torch::Tensor>& ins,
                        e.lds_bytes, cur_stream(), jobs, njobs, (int)N);
 }
 
+// Blocks of L's weight-grad kernel that the current device holds at once;
+// asked of the runtime on the first call per (geometry, device) (a host-side
+// query: nothing is enqueued) and kept. Threads that race on an empty slot
+// all store the same value. The m-grid, and with it the summation order and
+// the last bits of gw, follows this figure: results are reproducible on one
+// device model, not across parts with another CU count or occupancy.
+int wrw_resident_blocks(const Conv3Launch& L) {
+  constexpr int kMaxDevices = 64;
+  static std::atomic<int> cache[std::size(kConv3Launches)][kMaxDevices] = {};
+  const int dev = at::cuda::current_device();
+  TORCH_CHECK(dev >= 0 && dev < kMaxDevices, "conv3x3p1_wrw: device index");
+  std::atomic<int>& slot = cache[&L - kConv3Launches][dev];
+  int r = slot.load(std::memory_order_relaxed);
+  if (r == 0) {
+    int per_cu = 0;
+    TORCH_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &per_cu, (const void*)L.wrw, 256, L.wrw_lds_bytes) ==
+                        hipSuccess && per_cu > 0,
+                "conv3x3p1_wrw: occupancy query failed");
+    r = per_cu * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    slot.store(r, std::memory_order_relaxed);
+  }
+  return r;
+}
+
+// Ordered fold shared by every weight-grad: wrw_reduce_kernel sums the mb
+// partial planes of `part` into gw_ws (fp32 workspace, or bf16 = the
+// gradient itself); with bias, colsum's per-block column sums of gout
+// (M, COUT) fold into gb_ws in the same launch.
+void launch_wrw_fold(const torch::Tensor& part, int mb,
+                     const torch::Tensor& gout, int M, int64_t COUT,
+                     void (*colsum)(const __bf16*, int64_t, float*),
+                     torch::Tensor& gw_ws, torch::Tensor& gb_ws, bool bias) {
+  constexpr int kColsumBlocks = 256;
+  auto st = cur_stream();
+  const int n_elem = (int)gw_ws.numel();
+  const bool bf16_out = gw_ws.scalar_type() == kBF16;
+  torch::Tensor b_part;
+  if (bias) {
+    b_part = torch::empty({(int64_t)kColsumBlocks, COUT}, part.options());
+    hipLaunchKernelGGL(colsum, dim3(kColsumBlocks), dim3(256), 0, st,
+                       (const __bf16*)gout.data_ptr(), (int64_t)M,
+                       b_part.data_ptr<float>());
+  }
+  const int e_blocks = (n_elem + 63) / 64;
+  const float* b_part_ptr =
+      bias ? (const float*)b_part.data_ptr<float>() : nullptr;
+  if (bf16_out)
+    hipLaunchKernelGGL(wrw_reduce_kernel<__bf16>,
+                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), mb, n_elem,
+                       (__bf16*)gw_ws.data_ptr(), b_part_ptr, kColsumBlocks,
+                       (int)COUT, bias ? (__bf16*)gb_ws.data_ptr() : nullptr);
+  else
+    hipLaunchKernelGGL(wrw_reduce_kernel<float>,
+                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), mb, n_elem,
+                       gw_ws.data_ptr<float>(), b_part_ptr, kColsumBlocks,
+                       (int)COUT, bias ? gb_ws.data_ptr<float>() : nullptr);
+}
+
+// what each tensor of a launch_conv3 call is named in its error messages
+struct Conv3Labels {
+  const char *in, *out, *bias, *residual, *mask;
+};
+
+// The one launch path of conv3x3p1_fwd_kernel (forward and input gradient):
+// in (N,C,H,W) / out (N,COUT,H,W) logical channels_last bf16; w is COUT*9C
+// checked bf16 elements in (cout, kh, kw, c) order; residual and mask are
+// empty or shaped like out. mask selects the MASK instantiation. With
+// flip_from (a checked (COUT', C', 3, 3) weight of the same numel), w is a
+// workspace that conv3x3_w_flip_kernel fills first — after every check, so
+// a rejected call launches nothing.
+void launch_conv3(const torch::Tensor& in, const __bf16* w,
+                  const __bf16* flip_from, const torch::Tensor& bias,
+                  const torch::Tensor& residual, const torch::Tensor& mask,
+                  const torch::Tensor& out, int64_t COUT, bool relu_in,
+                  bool relu_out, const Conv3Labels& lb) {
+  const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
+  check_nhwc(in, kBF16, N, C, H, W, lb.in);
+  check_nhwc(out, kBF16, N, COUT, H, W, lb.out);
+  TORCH_CHECK(out.data_ptr() != in.data_ptr(), lb.out, " must not alias ",
+              lb.in, " (not in-place)");
+  // 16-byte pieces of in / weight, 8-byte pieces of out / residual / mask
+  TORCH_CHECK((uintptr_t)in.data_ptr() % 16 == 0, lb.in, " is misaligned");
+  TORCH_CHECK((uintptr_t)w % 16 == 0, lb.in, "'s weight is misaligned");
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 8 == 0, lb.out, " is misaligned");
+  const Conv3Launch* L = find_conv3(H, W, C, COUT);
+  TORCH_CHECK(L, "no 3x3 pad-1 conv kernel for this geometry: ", H, "x", W, "x",
+              C, " -> ", COUT);
+  const int M = checked_rows(N * H * W, lb.out);
+  const __bf16* bias_ptr = opt_vec(bias, COUT, lb.bias);
+  // optional tensor shaped like out: undefined or empty means "none"
+  auto like_out = [&](const torch::Tensor& t, const char* what) {
+    if (!t.defined() || t.numel() == 0) return (const __bf16*)nullptr;
+    check_nhwc(t, kBF16, N, COUT, H, W, what);
+    TORCH_CHECK((uintptr_t)t.data_ptr() % 8 == 0, what, " is misaligned");
+    return (const __bf16*)t.data_ptr();
+  };
+  const __bf16* res_ptr = like_out(residual, lb.residual);
+  const __bf16* mask_ptr = like_out(mask, lb.mask);
+  if (N == 0) return;
+  if (flip_from) {
+    // W'[ci][tap][co]: the flipped weight's (cout', c') = (C, COUT) here
+    const int total = (int)(9 * C * COUT);
+    hipLaunchKernelGGL(conv3x3_w_flip_kernel, dim3((total + 255) / 256),
+                       dim3(256), 0, cur_stream(), flip_from,
+                       const_cast<__bf16*>(w), (int)COUT, (int)C);
+  }
+  const int rows_per_block = L->waves * L->rpw;
+  const int blocks = (M + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(mask_ptr ? L->fn_mask : L->fn, dim3(blocks),
+                     dim3(L->waves * 64), L->lds_bytes, cur_stream(),
+                     (const __bf16*)in.data_ptr(), w, bias_ptr, res_ptr,
+                     mask_ptr, (__bf16*)out.data_ptr(), (int)N,
+                     relu_in ? 1 : 0, relu_out ? 1 : 0);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1355,29 +1728,7 @@ void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
                      st, (const void*)in.data_ptr(),
                      (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
                      (int)N, mb);
-  constexpr int kColsumBlocks = 256;
-  torch::Tensor b_part;
-  if (bias) {
-    b_part = torch::empty({(int64_t)kColsumBlocks, COUT}, f32);
-    hipLaunchKernelGGL(L->colsum, dim3(kColsumBlocks), dim3(256), 0, st,
-                       (const __bf16*)gout.data_ptr(), (int64_t)M,
-                       b_part.data_ptr<float>());
-  }
-  const int e_blocks = (n_elem + 63) / 64;
-  const float* b_part_ptr =
-      bias ? (const float*)b_part.data_ptr<float>() : nullptr;
-  if (bf16_out)
-    hipLaunchKernelGGL(wrw_reduce_kernel<__bf16>,
-                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
-                       (const float*)part.data_ptr<float>(), mb, n_elem,
-                       (__bf16*)gw_ws.data_ptr(), b_part_ptr, kColsumBlocks,
-                       (int)COUT, bias ? (__bf16*)gb_ws.data_ptr() : nullptr);
-  else
-    hipLaunchKernelGGL(wrw_reduce_kernel<float>,
-                       dim3(e_blocks + (bias ? 1 : 0)), dim3(256), 0, st,
-                       (const float*)part.data_ptr<float>(), mb, n_elem,
-                       gw_ws.data_ptr<float>(), b_part_ptr, kColsumBlocks,
-                       (int)COUT, bias ? gb_ws.data_ptr<float>() : nullptr);
+  launch_wrw_fold(part, mb, gout, M, COUT, L->colsum, gw_ws, gb_ws, bias);
 }
 
 bool conv_dgrad_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
@@ -1473,37 +1824,97 @@ void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
                    torch::Tensor residual, torch::Tensor out, bool relu_in,
                    bool relu_out) {
   TORCH_CHECK(in.dim() == 4 && weight.dim() == 4);
-  const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
   const int64_t COUT = weight.size(0);
-  check_nhwc(in, kBF16, N, C, H, W, "conv3x3p1_fwd input");
-  check_nhwc(weight, kBF16, COUT, C, 3, 3, "conv3x3p1_fwd weight");
-  check_nhwc(out, kBF16, N, COUT, H, W, "conv3x3p1_fwd output");
-  TORCH_CHECK(out.data_ptr() != in.data_ptr(), "conv3x3p1_fwd is not in-place");
-  // 16-byte pieces of in / weight, 8-byte pieces of out / residual
-  TORCH_CHECK((uintptr_t)in.data_ptr() % 16 == 0 &&
-                  (uintptr_t)weight.data_ptr() % 16 == 0 &&
-                  (uintptr_t)out.data_ptr() % 8 == 0,
-              "conv3x3p1_fwd: misaligned tensor");
+  check_nhwc(weight, kBF16, COUT, in.size(1), 3, 3, "conv3x3p1_fwd weight");
+  launch_conv3(in, (const __bf16*)weight.data_ptr(), nullptr, bias, residual,
+               torch::Tensor(), out, COUT, relu_in, relu_out,
+               {"conv3x3p1_fwd input", "conv3x3p1_fwd output",
+                "conv3x3p1_fwd bias", "conv3x3p1_fwd residual",
+                "conv3x3p1_fwd mask"});
+}
+
+bool conv3x3p1_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   const Conv3Launch* L = find_conv3(H, W, C, COUT);
-  TORCH_CHECK(L, "no 3x3 pad-1 conv kernel for this geometry: ", H, "x", W, "x",
-              C, " -> ", COUT);
-  const int M = checked_rows(N * H * W, "conv3x3p1_fwd");
-  const __bf16* bias_ptr = opt_vec(bias, COUT, "conv3x3p1_fwd bias");
-  const __bf16* res_ptr = nullptr;
-  if (residual.defined() && residual.numel() > 0) {
-    check_nhwc(residual, kBF16, N, COUT, H, W, "conv3x3p1_fwd residual");
-    TORCH_CHECK((uintptr_t)residual.data_ptr() % 8 == 0,
-                "conv3x3p1_fwd: misaligned residual");
-    res_ptr = (const __bf16*)residual.data_ptr();
-  }
-  if (N == 0) return;
-  const int rows_per_block = L->waves * L->rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), L->lds_bytes,
-                     cur_stream(), (const __bf16*)in.data_ptr(),
-                     (const __bf16*)weight.data_ptr(), bias_ptr, res_ptr,
-                     (__bf16*)out.data_ptr(), (int)N, relu_in ? 1 : 0,
-                     relu_out ? 1 : 0);
+  return L && L->wrw;
+}
+
+// x: (N,C,H,W) and gout: (N,COUT,H,W) logical channels_last bf16 (gout
+// already relu-masked); gw: (COUT, 9C) fp32 workspace, or the bf16 gradient
+// itself in (cout, kh, kw, c) memory order; gb: (COUT) of gw's dtype, or
+// empty — conv_wrw's contracts. relu_in: the conv read relu(x).
+void conv3x3p1_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
+                   torch::Tensor gb, bool relu_in) {
+  TORCH_CHECK(x.dim() == 4 && gout.dim() == 4,
+              "conv3x3p1_wrw wants 4-D x and gout");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t COUT = gout.size(1);
+  const Conv3Launch* L = find_conv3(H, W, C, COUT);
+  TORCH_CHECK(L && L->wrw, "no 3x3 pad-1 wrw kernel for this geometry: ", H,
+              "x", W, "x", C, " -> ", COUT);
+  check_nhwc(x, kBF16, N, C, H, W, "conv3x3p1_wrw x");
+  check_nhwc(gout, kBF16, N, COUT, H, W, "conv3x3p1_wrw gout (x's batch)");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)gout.data_ptr() % 16 == 0,
+              "conv3x3p1_wrw: misaligned tensor");
+  const bool bf16_out = gw.scalar_type() == kBF16;
+  check_dev(gw, bf16_out ? kBF16 : torch::kFloat32, "conv3x3p1_wrw gw");
+  TORCH_CHECK(gw.is_contiguous() ||
+                  (gw.dim() == 4 &&
+                   gw.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              "conv3x3p1_wrw gw must be dense in (cout, kh, kw, c) order");
+  const int64_t n_elem = COUT * 9 * C;
+  TORCH_CHECK(gw.numel() == n_elem, "conv3x3p1_wrw gw must hold ", n_elem,
+              " elements, got ", gw.numel());
+  const bool bias = gb.defined() && gb.numel() > 0;
+  if (bias) check_rows(gb, gw.scalar_type(), {COUT}, "conv3x3p1_wrw gb");
+  // the last pass's row numbers run past M by less than a pass
+  const int M = checked_rows(N * H * W + L->wrw_rows, "conv3x3p1_wrw") -
+                L->wrw_rows;
+  const int n_pass = (M + L->wrw_rows - 1) / L->wrw_rows;
+  // m-grid from M, the smallest of three: a block should meet at least 8
+  // passes, so the plane it writes (and the fold reads back) stays well
+  // below the input bytes it streams; all planes together stay within
+  // 16 MiB; and no more blocks than are resident at once (a second,
+  // part-filled round of blocks would only add planes)
+  const int64_t plane_bytes = (n_elem + kPlanePad) * 4;
+  int mb = (n_pass + 7) / 8;
+  const int mb_cap = (int)(((int64_t)16 << 20) / plane_bytes);
+  if (mb > mb_cap) mb = mb_cap;
+  const int resident = wrw_resident_blocks(*L);
+  if (mb > resident) mb = resident;
+  if (mb < 1) mb = 1;
+  const auto f32 = gw.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)mb, n_elem + kPlanePad}, f32);
+  hipLaunchKernelGGL(L->wrw, dim3(mb), dim3(256), L->wrw_lds_bytes,
+                     cur_stream(), (const __bf16*)x.data_ptr(),
+                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                     (int)N, mb, relu_in ? 1 : 0);
+  launch_wrw_fold(part, mb, gout, M, COUT, L->colsum, gw, gb, bias);
+}
+
+// Input gradient of the conv (x -> out, weight (COUT,C,3,3)) through the
+// forward kernel at the mirrored geometry: gx = conv3x3p1(gout, W').
+// gout: (N,COUT,H,W); weight: (COUT,C,3,3); w_flip_ws: COUT*C*9 bf16
+// workspace (overwritten with W'); gx: (N,C,H,W); mask_x: empty, or the
+// conv's input x — gx is then zeroed where x <= 0 (relu_in backward). All
+// logical channels_last bf16. Two launches, no allocation (graph-safe).
+void conv3x3p1_dgrad(torch::Tensor gout, torch::Tensor weight,
+                     torch::Tensor w_flip_ws, torch::Tensor gx,
+                     torch::Tensor mask_x) {
+  TORCH_CHECK(gout.dim() == 4 && weight.dim() == 4 && gx.dim() == 4,
+              "conv3x3p1_dgrad wants 4-D gout, weight and gx");
+  const int64_t COUT = weight.size(0), C = weight.size(1);
+  TORCH_CHECK(gout.size(1) == COUT, "conv3x3p1_dgrad: gout has ",
+              gout.size(1), " channels, weight ", COUT);
+  TORCH_CHECK(gx.size(0) == gout.size(0), "conv3x3p1_dgrad: batch mismatch");
+  check_nhwc(weight, kBF16, COUT, C, 3, 3, "conv3x3p1_dgrad weight");
+  check_rows(w_flip_ws, kBF16, {weight.numel()}, "conv3x3p1_dgrad w_flip_ws");
+  launch_conv3(gout, (const __bf16*)w_flip_ws.data_ptr(),
+               (const __bf16*)weight.data_ptr(), torch::Tensor(),
+               torch::Tensor(), mask_x, gx, C, false, false,
+               {"conv3x3p1_dgrad gout", "conv3x3p1_dgrad gx",
+                "conv3x3p1_dgrad bias", "conv3x3p1_dgrad residual",
+                "conv3x3p1_dgrad mask_x"});
 }
 
 void register_conv(pybind11::module_& m) {
@@ -1530,4 +1941,11 @@ void register_conv(pybind11::module_& m) {
         "MFMA 3x3 s1 pad-1 NHWC bf16 conv fwd (+relu_in, bias, residual, "
         "relu_out)");
   m.def("conv3x3p1_supported", &conv3x3p1_supported);
+  m.def("conv3x3p1_wrw", &conv3x3p1_wrw,
+        "MFMA 3x3 s1 pad-1 weight-grad (+relu_in); gw/gb are fp32 workspaces "
+        "or bf16 grads");
+  m.def("conv3x3p1_wrw_supported", &conv3x3p1_wrw_supported);
+  m.def("conv3x3p1_dgrad", &conv3x3p1_dgrad,
+        "3x3 s1 pad-1 input-grad: weight flip + the forward kernel at the "
+        "mirrored geometry (+relu_in mask in the epilogue)");
 }
