@@ -348,6 +348,31 @@ def _resconv_ok(x: torch.Tensor, *convs: nn.Conv2d) -> bool:
     return True
 
 
+def _pool_ok(x: torch.Tensor, pool: nn.MaxPool2d) -> bool:
+    """Own max-pool path (ops/hip/conv_mfma.hip maxpool3x3s2_*_kernel):
+    kernel 3, stride 2, padding 1, dilation 1, floor mode; CUDA bf16
+    channels_last input at a supported geometry; gate DRL_OWN_POOL ('1' own
+    kernel, '0' library, unset: the measured default of
+    profiles/r07_maxpool.md)."""
+
+    def pair(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+    if pair(pool.kernel_size) != (3, 3) or pair(pool.stride) != (2, 2) \
+            or pair(pool.padding) != (1, 1) or pair(pool.dilation) != (1, 1) \
+            or pool.ceil_mode or pool.return_indices:
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        return False
+    from .. import ops as _ops
+
+    if not _ops._gate("DRL_OWN_POOL", _ops._POOL_DEFAULT):
+        return False
+    return _ops.maxpool3x3s2_supported(x.shape[2], x.shape[3], x.shape[1])
+
+
 class ResidualBlock(nn.Module):
     def __init__(self, ch: int):
         super().__init__()
@@ -377,8 +402,11 @@ class ImpalaResNet(nn.Module):
 
     On bf16 channels_last GPU input the 3x3 pad-1 convs whose geometry the
     hand-written kernel covers (everything but the first, C=4 conv at
-    84x84) run through ops.fused_conv3x3 when DRL_OWN_RESCONV allows;
-    pooling, the first conv and the final ReLU+flatten stay in torch."""
+    84x84) run through ops.fused_conv3x3 when DRL_OWN_RESCONV allows, and
+    the 3x3 stride-2 pad-1 max-pools through ops.fused_maxpool3x3s2 (uint8
+    tap plane, gather backward without atomics) when DRL_OWN_POOL allows.
+    The two gates are independent and are read per layer. The first conv
+    and the final ReLU+flatten stay in torch."""
 
     def __init__(self, cfg: Dict[str, Any]):
         super().__init__()
@@ -396,14 +424,19 @@ class ImpalaResNet(nn.Module):
         self.body = nn.Sequential(*sections)
 
     def forward(self, x):
-        if x.is_cuda and x.dtype == torch.bfloat16 and _resconv_gate():
+        if x.is_cuda and x.dtype == torch.bfloat16:
             from .. import ops as _ops
 
+            # each layer decides for itself: the conv and pool gates are
+            # independent, and a layer nothing claims runs as nn.Sequential
+            # would run it
             y = x
             for layer in self.body:
                 if isinstance(layer, nn.Conv2d) and _resconv_ok(y, layer):
                     # section-entry conv: no flags
                     y = _ops.fused_conv3x3(y, layer.weight, layer.bias)
+                elif isinstance(layer, nn.MaxPool2d) and _pool_ok(y, layer):
+                    y = _ops.fused_maxpool3x3s2(y)
                 else:
                     y = layer(y)
         else:

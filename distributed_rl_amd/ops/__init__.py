@@ -424,6 +424,61 @@ def fused_conv3x3(x, weight, bias, *, relu_in: bool = False,
     return torch_ref.conv3x3_res(x, weight, bias, relu_in, relu_out, residual)
 
 
+def maxpool3x3s2_supported(H, W, C) -> bool:
+    ext = hip_ext(required=False)
+    return ext is not None and bool(ext.maxpool3x3s2_supported(H, W, C))
+
+
+# default of DRL_OWN_POOL (read by models/base_agent.py), decided by the A/B
+# in profiles/r07_maxpool.md: medians 4.433 (own pool) vs 5.543 ms/step for
+# the parent, 5.545 with the gate at 0, repeat spread at most 0.014 ms -> on
+_POOL_DEFAULT = True
+
+
+class _MaxPool3x3S2Fn(torch.autograd.Function):
+    """Forward on maxpool3x3s2_fwd_kernel; saves the uint8 tap plane only
+    (not x), and not even that when no gradient is wanted. Backward is the
+    ordered gather maxpool3x3s2_bwd_kernel: no zero fill, no atomics."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ext = hip_ext()
+        N, C, H, W = x.shape
+        P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        out = torch.empty(N, C, P, Q, dtype=torch.bfloat16, device=x.device,
+                          memory_format=torch.channels_last)
+        if ctx.needs_input_grad[0]:
+            idx = torch.empty(N, C, P, Q, dtype=torch.uint8, device=x.device,
+                              memory_format=torch.channels_last)
+        else:
+            idx = torch.empty(0, dtype=torch.uint8, device=x.device)
+        ext.maxpool3x3s2_fwd(x, out, idx)
+        ctx.save_for_backward(idx)
+        ctx.hw = (H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (idx,) = ctx.saved_tensors
+        if not gout.is_contiguous(memory_format=torch.channels_last):
+            gout = gout.contiguous(memory_format=torch.channels_last)
+        N, C = gout.shape[:2]
+        gx = torch.empty(N, C, *ctx.hw, dtype=torch.bfloat16,
+                         device=gout.device,
+                         memory_format=torch.channels_last)
+        hip_ext().maxpool3x3s2_bwd(gout, idx, gx)
+        return gx
+
+
+def fused_maxpool3x3s2(x):
+    """Max-pool kernel 3, stride 2, padding 1 (dilation 1, floor mode).
+    Device tensors must be bf16 channels_last with C % 16 == 0; CPU tensors
+    take the eager reference."""
+    if _use_hip(x):
+        return _MaxPool3x3S2Fn.apply(x)
+    return torch_ref.maxpool3x3s2(x)
+
+
 def linear_relu_supported(K, N) -> bool:
     ext = hip_ext(required=False)
     return ext is not None and hasattr(ext, "linear_relu_supported") and \

@@ -1252,6 +1252,178 @@ const Conv3Launch* find_conv3(int64_t H, int64_t W, int64_t C, int64_t COUT) {
 }
 
 // ===========================================================================
+// Max-pool 3x3 stride 2 pad 1 (dilation 1, floor mode) of the torso, NHWC
+// bf16, forward and backward. H, W and C are run-time values, C % 16 == 0;
+// P = (H-1)/2 + 1, Q = (W-1)/2 + 1. Both kernels stream: one lane owns 16
+// channels of one pixel (two 16-byte pieces), lanes run along (n, row, col,
+// channel group), so a wave reads and writes contiguous memory.
+//
+//   * forward: lane = output pixel. Taps are scanned in (kh, kw) order; the
+//     first in-bounds tap initialises maximum and index, a later one
+//     replaces them iff v > m || isnan(v) (the library's rule: ties keep
+//     the earliest tap, +0/-0 do not replace each other, NaN propagates and
+//     the last NaN takes the index). Written here as m = -inf, index =
+//     first in-bounds tap, then the rule over every in-bounds tap: the first
+//     either replaces (v > -inf or NaN) or is -inf itself. The winner's
+//     bf16 bits are stored as they are. An out-of-bounds tap is never
+//     loaded. The index plane is uint8, same shape and layout as out,
+//     holding kh*3 + kw; WITH_IDX=false drops it (no gradient wanted).
+//   * backward: a gather, lane = INPUT pixel (h, w). Row h lies in window
+//     po = h/2 at kh = 1 (h even), or in po = (h-1)/2 at kh = 2 and
+//     po = (h+1)/2 (if < P) at kh = 0 (h odd); columns alike: 1, 2 or 4
+//     windows. gx = sum of gout[po,qo] where idx[po,qo] names this pixel's
+//     tap, in ascending (po, qo) order, in f32, rounded to bf16 once. Every
+//     gx element is written exactly once: no zero fill, no atomics, and the
+//     result does not depend on scheduling.
+// ===========================================================================
+
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+
+template <bool WITH_IDX>
+__global__ __launch_bounds__(256) void maxpool3x3s2_fwd_kernel(
+    const __bf16* __restrict__ x,  // (N,H,W,C)
+    __bf16* __restrict__ out,      // (N,P,Q,C)
+    uint8_t* __restrict__ idx,     // (N,P,Q,C), WITH_IDX only
+    int lanes,                     // N*P*Q*CG
+    int H, int W, int P, int Q, int CG) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)lanes) return;
+  const unsigned pix = i / (unsigned)CG;  // (n*P + p)*Q + q
+  const unsigned cg = i - pix * (unsigned)CG;
+  const unsigned np = pix / (unsigned)Q;
+  const int q = (int)(pix - np * (unsigned)Q);
+  const unsigned n = np / (unsigned)P;
+  const int p = (int)(np - n * (unsigned)P);
+  const int C = CG * 16;
+  const int h0 = 2 * p - 1, w0 = 2 * q - 1;
+  const __bf16* xin = x + (int64_t)n * H * W * C + cg * 16;
+
+  float m[16];
+  unsigned ix[16];
+  const unsigned first = (p == 0 ? 3u : 0u) + (q == 0 ? 1u : 0u);
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    m[c] = -__builtin_inff();
+    ix[c] = first;
+  }
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh) {
+    const int h = h0 + kh;
+    // a row's three taps go in flight together
+    u32x4 v[3][2] = {};
+    bool live[3];
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int w = w0 + kw;
+      live[kw] = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+      if (live[kw]) {
+        const u32x4* s =
+            reinterpret_cast<const u32x4*>(xin + ((int64_t)h * W + w) * C);
+        v[kw][0] = s[0];
+        v[kw][1] = s[1];
+      }
+    }
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      if (!live[kw]) continue;
+      const unsigned tap = kh * 3 + kw;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) {
+        // bf16 -> f32 is the bits moved up: compare in f32, keep the bits
+        const unsigned word = v[kw][c >> 3][(c >> 1) & 3];
+        const float f = __builtin_bit_cast(
+            float, (c & 1) ? (word & 0xffff0000u) : (word << 16));
+        const bool take = f > m[c] || f != f;
+        m[c] = take ? f : m[c];
+        ix[c] = take ? tap : ix[c];
+      }
+    }
+  }
+
+  const int64_t o = (int64_t)pix * C + cg * 16;
+  u32x4 ov[2];
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    ov[j >> 2][j & 3] = (__builtin_bit_cast(unsigned, m[2 * j]) >> 16) |
+                        (__builtin_bit_cast(unsigned, m[2 * j + 1]) &
+                         0xffff0000u);
+  u32x4* od = reinterpret_cast<u32x4*>(out + o);
+  od[0] = ov[0];
+  od[1] = ov[1];
+  if constexpr (WITH_IDX) {
+    u32x4 iv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      iv[j] = ix[4 * j] | (ix[4 * j + 1] << 8) | (ix[4 * j + 2] << 16) |
+              (ix[4 * j + 3] << 24);
+    *reinterpret_cast<u32x4*>(idx + o) = iv;
+  }
+}
+
+__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(
+    const __bf16* __restrict__ gout,  // (N,P,Q,C)
+    const uint8_t* __restrict__ idx,  // (N,P,Q,C)
+    __bf16* __restrict__ gx,          // (N,H,W,C)
+    int lanes,                        // N*H*W*CG
+    int H, int W, int P, int Q, int CG) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)lanes) return;
+  const unsigned pix = i / (unsigned)CG;  // (n*H + h)*W + w
+  const unsigned cg = i - pix * (unsigned)CG;
+  const unsigned nh = pix / (unsigned)W;
+  const int w = (int)(pix - nh * (unsigned)W);
+  const unsigned n = nh / (unsigned)H;
+  const int h = (int)(nh - n * (unsigned)H);
+  const int C = CG * 16;
+  const int64_t img = (int64_t)n * P * Q * C + cg * 16;
+
+  float acc[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) acc[c] = 0.f;
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    const int po = (h >> 1) + a;
+    const int kh = h + 1 - 2 * po;  // 1 | 2 then 0
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int qo = (w >> 1) + b;
+      const int kw = w + 1 - 2 * qo;
+      // the second window exists for odd coordinates only, and not past
+      // the last one
+      const bool live = (a == 0 || ((h & 1) && po < P)) &&
+                        (b == 0 || ((w & 1) && qo < Q));
+      if (!live) continue;
+      const int64_t o = img + ((int64_t)po * Q + qo) * C;
+      const u32x4 iv = *reinterpret_cast<const u32x4*>(idx + o);
+      const u32x4* gs = reinterpret_cast<const u32x4*>(gout + o);
+      const u32x4 g0 = gs[0], g1 = gs[1];
+      const unsigned tap = (unsigned)(kh * 3 + kw);
+#pragma unroll
+      for (int c = 0; c < 16; ++c) {
+        const unsigned word = (c < 8 ? g0 : g1)[(c >> 1) & 3];
+        const float g = __builtin_bit_cast(
+            float, (c & 1) ? (word & 0xffff0000u) : (word << 16));
+        const unsigned t = (iv[c >> 2] >> (8 * (c & 3))) & 0xffu;
+        acc[c] += t == tap ? g : 0.f;
+      }
+    }
+  }
+
+  u32x4 ov[2];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const unsigned lo =
+        __builtin_bit_cast(unsigned short, (__bf16)acc[2 * j]);
+    const unsigned hi =
+        __builtin_bit_cast(unsigned short, (__bf16)acc[2 * j + 1]);
+    ov[j >> 2][j & 3] = lo | (hi << 16);
+  }
+  u32x4* od = reinterpret_cast<u32x4*>(gx + (int64_t)pix * C + cg * 16);
+  od[0] = ov[0];
+  od[1] = ov[1];
+}
+
+// ===========================================================================
 // Geometry table of the strided no-pad convs: ONE entry per
 // (H, W, C, KH, KW, S, COUT, u8) carries every kernel of that geometry, so
 // a new geometry or variant is one line here.
@@ -1917,6 +2089,73 @@ void conv3x3p1_dgrad(torch::Tensor gout, torch::Tensor weight,
                 "conv3x3p1_dgrad mask_x"});
 }
 
+bool maxpool3x3s2_supported(int64_t H, int64_t W, int64_t C) {
+  return H >= 1 && W >= 1 && C >= 16 && C % 16 == 0;
+}
+
+// x: (N,C,H,W), out: (N,C,P,Q) logical channels_last bf16; idx: uint8 of
+// out's shape and layout (winning tap kh*3 + kw), or empty: no index plane
+// is written (a forward that needs no gradient). One launch, no allocation.
+void maxpool3x3s2_fwd(torch::Tensor x, torch::Tensor out, torch::Tensor idx) {
+  TORCH_CHECK(x.dim() == 4, "maxpool3x3s2_fwd wants a 4-D x");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(maxpool3x3s2_supported(H, W, C),
+              "no 3x3 s2 max-pool kernel for this geometry: ", H, "x", W, "x",
+              C);
+  const int64_t P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1;
+  check_nhwc(x, kBF16, N, C, H, W, "maxpool3x3s2_fwd x");
+  check_nhwc(out, kBF16, N, C, P, Q, "maxpool3x3s2_fwd out");
+  const bool with_idx = idx.defined() && idx.numel() > 0;
+  if (with_idx)
+    check_nhwc(idx, torch::kUInt8, N, C, P, Q, "maxpool3x3s2_fwd idx");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)out.data_ptr() % 16 == 0 &&
+                  (!with_idx || (uintptr_t)idx.data_ptr() % 16 == 0),
+              "maxpool3x3s2_fwd: misaligned tensor");
+  // the kernel numbers input pixels with int as well
+  checked_rows(N * H * W, "maxpool3x3s2_fwd");
+  const int lanes = checked_rows(N * P * Q * (C / 16), "maxpool3x3s2_fwd");
+  if (lanes == 0) return;
+  const dim3 grid((unsigned)(((int64_t)lanes + 255) / 256));
+  if (with_idx)
+    hipLaunchKernelGGL(maxpool3x3s2_fwd_kernel<true>, grid, dim3(256), 0,
+                       cur_stream(), (const __bf16*)x.data_ptr(),
+                       (__bf16*)out.data_ptr(), (uint8_t*)idx.data_ptr(),
+                       lanes, (int)H, (int)W, (int)P, (int)Q, (int)(C / 16));
+  else
+    hipLaunchKernelGGL(maxpool3x3s2_fwd_kernel<false>, grid, dim3(256), 0,
+                       cur_stream(), (const __bf16*)x.data_ptr(),
+                       (__bf16*)out.data_ptr(), (uint8_t*)nullptr, lanes,
+                       (int)H, (int)W, (int)P, (int)Q, (int)(C / 16));
+}
+
+// gout: (N,C,P,Q) bf16 and idx: uint8 of the same shape, as the forward
+// left them; gx: (N,C,H,W) bf16, every element written. All logical
+// channels_last. One launch, no allocation, no atomics.
+void maxpool3x3s2_bwd(torch::Tensor gout, torch::Tensor idx,
+                      torch::Tensor gx) {
+  TORCH_CHECK(gx.dim() == 4, "maxpool3x3s2_bwd wants a 4-D gx");
+  const int64_t N = gx.size(0), C = gx.size(1), H = gx.size(2), W = gx.size(3);
+  TORCH_CHECK(maxpool3x3s2_supported(H, W, C),
+              "no 3x3 s2 max-pool kernel for this geometry: ", H, "x", W, "x",
+              C);
+  const int64_t P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1;
+  check_nhwc(gout, kBF16, N, C, P, Q, "maxpool3x3s2_bwd gout");
+  check_nhwc(idx, torch::kUInt8, N, C, P, Q, "maxpool3x3s2_bwd idx");
+  check_nhwc(gx, kBF16, N, C, H, W, "maxpool3x3s2_bwd gx");
+  TORCH_CHECK((uintptr_t)gout.data_ptr() % 16 == 0 &&
+                  (uintptr_t)idx.data_ptr() % 16 == 0 &&
+                  (uintptr_t)gx.data_ptr() % 16 == 0,
+              "maxpool3x3s2_bwd: misaligned tensor");
+  const int lanes = checked_rows(N * H * W * (C / 16), "maxpool3x3s2_bwd");
+  if (lanes == 0) return;
+  const dim3 grid((unsigned)(((int64_t)lanes + 255) / 256));
+  hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, grid, dim3(256), 0, cur_stream(),
+                     (const __bf16*)gout.data_ptr(),
+                     (const uint8_t*)idx.data_ptr(), (__bf16*)gx.data_ptr(),
+                     lanes, (int)H, (int)W, (int)P, (int)Q, (int)(C / 16));
+}
+
 void register_conv(pybind11::module_& m) {
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA fragment-map probe");
   m.def("tr16_probe", &tr16_probe);
@@ -1948,4 +2187,11 @@ void register_conv(pybind11::module_& m) {
   m.def("conv3x3p1_dgrad", &conv3x3p1_dgrad,
         "3x3 s1 pad-1 input-grad: weight flip + the forward kernel at the "
         "mirrored geometry (+relu_in mask in the epilogue)");
+  m.def("maxpool3x3s2_fwd", &maxpool3x3s2_fwd,
+        "NHWC bf16 max-pool 3x3 s2 pad-1 fwd; uint8 tap plane, or none when "
+        "idx is empty");
+  m.def("maxpool3x3s2_bwd", &maxpool3x3s2_bwd,
+        "max-pool 3x3 s2 pad-1 input-grad: ordered gather over the tap "
+        "plane, every gx element written once");
+  m.def("maxpool3x3s2_supported", &maxpool3x3s2_supported);
 }

@@ -39,6 +39,60 @@ def conv3x3_res(x, weight, bias=None, relu_in: bool = False,
 
 
 # ---------------------------------------------------------------------------
+# K2c — max-pool 3x3 stride 2 pad 1 of the IMPALA-ResNet torso
+#       (models/base_agent.py ImpalaResNet: nn.MaxPool2d(3, 2, 1)); the
+#       winning tap kh*3 + kw per output element, and the input gradient as
+#       an ordered fp32 gather over that tap plane
+# ---------------------------------------------------------------------------
+
+
+def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
+    return torch.nn.functional.max_pool2d(x, 3, 2, 1)
+
+
+def maxpool3x3s2_taps(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out, taps): taps is uint8 of out's shape, the winner's position in its
+    window as kh*3 + kw, from the library's flat h*W + w index."""
+    W = x.shape[-1]
+    out, i = torch.nn.functional.max_pool2d(x, 3, 2, 1, return_indices=True)
+    P, Q = out.shape[-2:]
+    p = torch.arange(P, device=x.device).view(P, 1)
+    q = torch.arange(Q, device=x.device).view(1, Q)
+    tap = (i // W - (2 * p - 1)) * 3 + (i % W - (2 * q - 1))
+    return out, tap.to(torch.uint8)
+
+
+def maxpool3x3s2_bwd(gout: torch.Tensor, taps: torch.Tensor, H: int,
+                     W: int) -> torch.Tensor:
+    """fp32 input gradient: each input pixel sums gout over the windows whose
+    tap names it, in ascending (po, qo) order. Pixel h = 2*po - 1 + kh, so
+    per pixel a larger kh is the earlier window: taps run (kh, kw) from
+    (2, 2) down to (0, 0)."""
+    N, C, P, Q = gout.shape
+    g = gout.float()
+    zero = torch.zeros((), dtype=torch.float32, device=gout.device)
+    gx = torch.zeros(N, C, H, W, dtype=torch.float32, device=gout.device)
+
+    def span(k, size, n_win):
+        # windows [lo, hi) whose tap k lies inside [0, size)
+        lo = 1 if k == 0 else 0
+        hi = min(n_win, (size - k) // 2 + 1)
+        return lo, hi
+
+    for kh in (2, 1, 0):
+        p0, p1 = span(kh, H, P)
+        for kw in (2, 1, 0):
+            q0, q1 = span(kw, W, Q)
+            if p1 <= p0 or q1 <= q0:
+                continue
+            hit = taps[:, :, p0:p1, q0:q1] == kh * 3 + kw
+            h0, w0 = 2 * p0 - 1 + kh, 2 * q0 - 1 + kw
+            gx[:, :, h0:h0 + 2 * (p1 - p0):2, w0:w0 + 2 * (q1 - q0):2] += \
+                torch.where(hit, g[:, :, p0:p1, q0:q1], zero)
+    return gx
+
+
+# ---------------------------------------------------------------------------
 # K4 — n-step double-DQN TD loss + new priority + IS-weighted loss
 #      (APE_X/Learner.py:83-114; gamma**n with done mask; TD clip to [-1,1];
 #      priority (|clip(td)|+1e-7)**alpha; loss 0.5*mean(w*td^2))
