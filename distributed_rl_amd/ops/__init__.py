@@ -505,8 +505,10 @@ class _LinearReluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w, out = ctx.saved_tensors
+        # empty_like of a dense but permuted g would keep g's strides
+        g = g.contiguous()
         masked = torch.empty_like(g)
-        hip_ext().relu_mask_bwd(g.contiguous(), out, masked)
+        hip_ext().relu_mask_bwd(g, out, masked)
         dx = masked.mm(w) if ctx.needs_input_grad[0] else None
         dw = masked.t().mm(x) if ctx.needs_input_grad[1] else None
         db = (masked.float().sum(0).to(torch.bfloat16)

@@ -472,10 +472,52 @@ static inline hipStream_t cur_stream() {
   return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
 }
 
+// Host-side checks of the replay-path bindings: every tensor a kernel
+// addresses is checked for device, dtype, layout and element count before
+// anything is launched, and the message names the argument. Index VALUES
+// (sum-tree leaf indices, gather row indices) live on the device and cannot
+// be checked without a sync; they stay the caller's contract.
+namespace {
+void check_on(const torch::Tensor& t, at::ScalarType dtype,
+              const char* what) {
+  TORCH_CHECK(t.defined() && t.is_cuda(), what, " must be a device tensor");
+  TORCH_CHECK(t.scalar_type() == dtype, what, " must be ", dtype, ", got ",
+              t.scalar_type());
+}
+
+// contiguous n-element vector of dtype on ref's device
+void check_vec(const torch::Tensor& t, at::ScalarType dtype, int64_t n,
+               const torch::Tensor& ref, const char* what) {
+  check_on(t, dtype, what);
+  TORCH_CHECK(t.device() == ref.device(), what, " is on ", t.device(),
+              ", expected ", ref.device());
+  TORCH_CHECK(t.is_contiguous() && t.numel() == n, what,
+              " must be contiguous with ", n, " elements, got ", t.sizes());
+}
+
+// float tree[2P], P a power of two
+void check_tree(const torch::Tensor& tree, int64_t P) {
+  TORCH_CHECK(P >= 1 && (P & (P - 1)) == 0, "P must be a power of two, got ",
+              P);
+  check_on(tree, torch::kFloat32, "tree");
+  TORCH_CHECK(tree.is_contiguous() && tree.numel() == 2 * P,
+              "tree must be contiguous with 2P = ", 2 * P, " elements, got ",
+              tree.sizes());
+}
+
+// kernels index draws / updates with int
+int checked_count(int64_t n, const char* what) {
+  TORCH_CHECK(n < (int64_t)1 << 31, what, ": too many elements");
+  return (int)n;
+}
+}  // namespace
+
 void dequant(torch::Tensor src_u8, torch::Tensor dst) {
   DRL_CHECK_CUDA(src_u8);
   DRL_CHECK_CONTIG(src_u8);
+  DRL_CHECK_CUDA(dst);
   DRL_CHECK_CONTIG(dst);
+  TORCH_CHECK(dst.device() == src_u8.device(), "dst is on another device");
   TORCH_CHECK(src_u8.scalar_type() == torch::kUInt8);
   int64_t n = src_u8.numel();
   TORCH_CHECK(n % 4 == 0, "element count must be a multiple of 4");
@@ -501,8 +543,13 @@ void dequant_nhwc(torch::Tensor src_u8, torch::Tensor dst) {
   TORCH_CHECK(src_u8.scalar_type() == torch::kUInt8);
   TORCH_CHECK(dst.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(src_u8.dim() == 4 && src_u8.size(1) == 4, "expects (N,4,H,W)");
+  TORCH_CHECK(dst.is_cuda() && dst.device() == src_u8.device(),
+              "dst must be on src's device");
+  TORCH_CHECK(dst.sizes() == src_u8.sizes(), "dst must be ", src_u8.sizes(),
+              ", got ", dst.sizes());
   TORCH_CHECK(dst.is_contiguous(at::MemoryFormat::ChannelsLast),
               "dst must be channels_last");
+  if (src_u8.numel() == 0) return;
   int64_t N = src_u8.size(0), H = src_u8.size(2), W = src_u8.size(3);
   int64_t hw = H * W, n_pix = N * hw;
   hipLaunchKernelGGL(dequant_u8_bf16_nhwc_c4_kernel, dim3(grid_for(n_pix)),
@@ -513,10 +560,10 @@ void dequant_nhwc(torch::Tensor src_u8, torch::Tensor dst) {
 
 void sumtree_update(torch::Tensor tree, torch::Tensor idx, torch::Tensor prio,
                     int64_t P) {
-  DRL_CHECK_CUDA(tree);
-  TORCH_CHECK(idx.scalar_type() == torch::kInt64);
-  TORCH_CHECK(prio.scalar_type() == torch::kFloat32);
-  int m = (int)idx.numel();
+  check_tree(tree, P);
+  check_vec(idx, torch::kInt64, idx.numel(), tree, "idx");
+  check_vec(prio, torch::kFloat32, idx.numel(), tree, "prio");
+  int m = checked_count(idx.numel(), "idx");
   if (m == 0) return;
   int64_t top = P < kTreeTop ? P : kTreeTop;
   hipLaunchKernelGGL(sumtree_update_kernel, dim3(ceil_div(m, kBlock)), dim3(kBlock),
@@ -542,7 +589,14 @@ void sumtree_update(torch::Tensor tree, torch::Tensor idx, torch::Tensor prio,
 void sumtree_sample(torch::Tensor tree, int64_t P, int64_t n_valid, int64_t k,
                     torch::Tensor seed, torch::Tensor out_idx,
                     torch::Tensor out_prob) {
-  DRL_CHECK_CUDA(tree);
+  check_tree(tree, P);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= P, "n_valid must be in [1, P = ", P,
+              "], got ", n_valid);
+  TORCH_CHECK(k >= 1, "k must be at least 1, got ", k);
+  checked_count(k, "k");
+  check_vec(seed, torch::kInt64, 1, tree, "seed");
+  check_vec(out_idx, torch::kInt64, k, tree, "out_idx");
+  check_vec(out_prob, torch::kFloat32, k, tree, "out_prob");
   hipLaunchKernelGGL(sumtree_sample_kernel, dim3(ceil_div(k, kBlock)), dim3(kBlock),
                      0, cur_stream(), tree.data_ptr<float>(), P, n_valid, (int)k,
                      (const unsigned long long*)seed.data_ptr(),
@@ -551,6 +605,11 @@ void sumtree_sample(torch::Tensor tree, int64_t P, int64_t n_valid, int64_t k,
 
 void leaf_min_pos(torch::Tensor tree, int64_t P, int64_t n_valid,
                   torch::Tensor out_bits) {
+  check_tree(tree, P);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= P, "n_valid must be in [1, P = ", P,
+              "], got ", n_valid);
+  // the fp32 bit pattern of the running minimum, in one int32 word
+  check_vec(out_bits, torch::kInt32, 1, tree, "out_bits");
   hipLaunchKernelGGL(leaf_min_pos_kernel, dim3(grid_for(n_valid, 8)), dim3(kBlock),
                      0, cur_stream(), tree.data_ptr<float>(), P, n_valid,
                      (unsigned int*)out_bits.data_ptr());
@@ -558,7 +617,15 @@ void leaf_min_pos(torch::Tensor tree, int64_t P, int64_t n_valid,
 
 void per_weights(torch::Tensor prob, torch::Tensor min_bits, torch::Tensor tree,
                  int64_t n_valid, double beta, torch::Tensor out_w) {
-  int k = (int)prob.numel();
+  check_on(tree, torch::kFloat32, "tree");
+  TORCH_CHECK(tree.is_contiguous() && tree.numel() >= 2,
+              "tree must be a contiguous sum-tree, got ", tree.sizes());
+  TORCH_CHECK(n_valid >= 1, "n_valid must be at least 1, got ", n_valid);
+  check_vec(prob, torch::kFloat32, prob.numel(), tree, "prob");
+  check_vec(min_bits, torch::kInt32, 1, tree, "min_bits");
+  check_vec(out_w, torch::kFloat32, prob.numel(), tree, "out_w");
+  int k = checked_count(prob.numel(), "prob");
+  if (k == 0) return;
   hipLaunchKernelGGL(per_weights_kernel, dim3(ceil_div(k, kBlock)), dim3(kBlock), 0,
                      cur_stream(), prob.data_ptr<float>(),
                      (const unsigned int*)min_bits.data_ptr(),
@@ -567,6 +634,7 @@ void per_weights(torch::Tensor prob, torch::Tensor min_bits, torch::Tensor tree,
 }
 
 void bump_seed(torch::Tensor seed) {
+  check_vec(seed, torch::kInt64, 1, seed, "seed");
   hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(64), 0, cur_stream(),
                      (unsigned long long*)seed.data_ptr());
 }
@@ -890,10 +958,34 @@ __global__ void relu_mask_bwd_kernel(const ushort4* __restrict__ out,
 }  // namespace
 
 void relu_mask_bwd(torch::Tensor gout, torch::Tensor out, torch::Tensor dst) {
-  TORCH_CHECK(gout.scalar_type() == torch::kBFloat16 &&
-              out.scalar_type() == torch::kBFloat16);
+  // The kernel walks the three tensors as raw memory, element e of one
+  // against element e of the others: that is the same logical element only
+  // if they share sizes and strides and fill their memory without gaps. A
+  // size-1 dimension's stride addresses nothing and is not compared.
+  check_on(gout, torch::kBFloat16, "gout");
+  const torch::Tensor* ts[2] = {&out, &dst};
+  const char* names[2] = {"out", "dst"};
+  for (int i = 0; i < 2; ++i) {
+    const torch::Tensor& t = *ts[i];
+    check_on(t, torch::kBFloat16, names[i]);
+    TORCH_CHECK(t.device() == gout.device(), names[i], " is on ", t.device(),
+                ", expected ", gout.device());
+    TORCH_CHECK(t.sizes() == gout.sizes(), names[i], " must be ",
+                gout.sizes(), " like gout, got ", t.sizes());
+    for (int64_t d = 0; d < gout.dim(); ++d)
+      TORCH_CHECK(gout.size(d) <= 1 || t.stride(d) == gout.stride(d),
+                  names[i], " must have gout's strides ", gout.strides(),
+                  ", got ", t.strides());
+    TORCH_CHECK(t.is_non_overlapping_and_dense(), names[i],
+                " must be dense in its strides");
+    TORCH_CHECK((uintptr_t)t.data_ptr() % 8 == 0, names[i], " is misaligned");
+  }
+  TORCH_CHECK(gout.is_non_overlapping_and_dense(),
+              "gout must be dense in its strides");
+  TORCH_CHECK((uintptr_t)gout.data_ptr() % 8 == 0, "gout is misaligned");
   int64_t n = gout.numel();
-  TORCH_CHECK(n % 4 == 0);
+  TORCH_CHECK(n % 4 == 0, "element count must be a multiple of 4, got ", n);
+  if (n == 0) return;
   hipLaunchKernelGGL(relu_mask_bwd_kernel, dim3(grid_for(n / 4)), dim3(kBlock),
                      0, cur_stream(), (const ushort4*)out.data_ptr(),
                      (const ushort4*)gout.data_ptr(), (ushort4*)dst.data_ptr(),
@@ -2868,11 +2960,27 @@ __global__ void seq_transpose_rows_kernel(const uint4* __restrict__ src,
 
 void seq_transpose_rows(torch::Tensor src, torch::Tensor dst) {
   // src: (B, T, ...) contiguous; dst: (T, B, ...) contiguous, same dtype
+  TORCH_CHECK(src.defined() && src.is_cuda(), "src must be a device tensor");
+  TORCH_CHECK(src.dim() >= 2, "src must be (B, T, ...), got ", src.sizes());
+  check_on(dst, src.scalar_type(), "dst");
+  TORCH_CHECK(dst.device() == src.device(), "dst is on ", dst.device(),
+              ", expected ", src.device());
+  std::vector<int64_t> want(src.sizes().begin(), src.sizes().end());
+  std::swap(want[0], want[1]);
+  TORCH_CHECK(dst.sizes() == at::IntArrayRef(want), "dst must be ",
+              at::IntArrayRef(want), ", got ", dst.sizes());
+  TORCH_CHECK(src.is_contiguous(), "src must be contiguous");
+  TORCH_CHECK(dst.is_contiguous(), "dst must be contiguous");
+  if (src.numel() == 0) return;
+  TORCH_CHECK(src.size(0) * src.size(1) < (int64_t)1 << 31,
+              "src: too many rows");
   const int B = (int)src.size(0), T = (int)src.size(1);
   const int64_t row_bytes =
       src.numel() * src.element_size() / ((int64_t)B * T);
   TORCH_CHECK(row_bytes % 16 == 0, "row bytes must be 16-aligned");
-  TORCH_CHECK(src.is_contiguous() && dst.is_contiguous());
+  TORCH_CHECK(row_bytes / 16 < (int64_t)1 << 31, "src: row too long");
+  TORCH_CHECK((uintptr_t)src.data_ptr() % 16 == 0, "src is misaligned");
+  TORCH_CHECK((uintptr_t)dst.data_ptr() % 16 == 0, "dst is misaligned");
   hipLaunchKernelGGL(seq_transpose_rows_kernel, dim3(B * T), dim3(256), 0,
                      cur_stream(), (const uint4*)src.data_ptr(),
                      (uint4*)dst.data_ptr(), B, T, (int)(row_bytes / 16));
@@ -2921,17 +3029,42 @@ __global__ void gather_rows_kernel(GatherCols a,
 
 void gather_rows(torch::Tensor idx, std::vector<torch::Tensor> srcs,
                  std::vector<torch::Tensor> dsts) {
-  TORCH_CHECK(srcs.size() == dsts.size() && srcs.size() <= 8);
+  TORCH_CHECK(srcs.size() == dsts.size() && srcs.size() >= 1 &&
+                  srcs.size() <= 8,
+              "gather_rows takes 1..8 columns, one dst per src; got ",
+              srcs.size(), " srcs and ", dsts.size(), " dsts");
+  check_vec(idx, torch::kInt64, idx.numel(), idx, "idx");
+  const int k = checked_count(idx.numel(), "idx");
   GatherCols a{};
   a.ncols = (int)srcs.size();
   for (int c = 0; c < a.ncols; ++c) {
-    TORCH_CHECK(srcs[c].is_contiguous() && dsts[c].is_contiguous());
-    a.src[c] = (const uint8_t*)srcs[c].data_ptr();
-    a.dst[c] = (uint8_t*)dsts[c].data_ptr();
-    a.row_bytes[c] =
-        srcs[c].numel() * srcs[c].element_size() / srcs[c].size(0);
+    const torch::Tensor& s = srcs[c];
+    const torch::Tensor& d = dsts[c];
+    TORCH_CHECK(s.defined() && s.is_cuda() && s.device() == idx.device(),
+                "srcs[", c, "] must be on idx's device ", idx.device());
+    TORCH_CHECK(s.dim() >= 1 && s.size(0) > 0, "srcs[", c,
+                "] must have at least one row, got ", s.sizes());
+    TORCH_CHECK(s.is_contiguous(), "srcs[", c, "] must be contiguous");
+    TORCH_CHECK(d.defined() && d.is_cuda() && d.device() == idx.device(),
+                "dsts[", c, "] must be on idx's device ", idx.device());
+    TORCH_CHECK(d.scalar_type() == s.scalar_type(), "dsts[", c, "] must be ",
+                s.scalar_type(), " like its src, got ", d.scalar_type());
+    TORCH_CHECK(d.dim() >= 1 && d.size(0) == k, "dsts[", c, "] must have k = ",
+                k, " rows, got ", d.sizes());
+    TORCH_CHECK(d.is_contiguous(), "dsts[", c, "] must be contiguous");
+    a.src[c] = (const uint8_t*)s.data_ptr();
+    a.dst[c] = (uint8_t*)d.data_ptr();
+    a.row_bytes[c] = s.numel() * s.element_size() / s.size(0);
+    TORCH_CHECK(d.numel() * d.element_size() == (int64_t)k * a.row_bytes[c],
+                "dsts[", c, "] rows must be ", a.row_bytes[c],
+                " bytes like its src's, got ", d.sizes());
+    // 16-byte-multiple rows move as uint4 pieces
+    TORCH_CHECK((a.row_bytes[c] & 15) != 0 ||
+                    ((uintptr_t)a.src[c] % 16 == 0 &&
+                     (uintptr_t)a.dst[c] % 16 == 0),
+                "column ", c, " is misaligned for 16-byte pieces");
   }
-  const int k = (int)idx.numel();
+  if (k == 0) return;
   int64_t max_rb = 0;
   for (int c = 0; c < a.ncols; ++c)
     max_rb = a.row_bytes[c] > max_rb ? a.row_bytes[c] : max_rb;

@@ -258,6 +258,84 @@ def per_is_weights(
 
 
 # ---------------------------------------------------------------------------
+# K10 kernel oracles — the sum-tree itself, operation by operation. Every step
+# of the device kernels is one correctly rounded fp32 operation (or 64-bit
+# integer arithmetic), so these reproduce them bit for bit: numpy float32
+# arrays round once per operation, uint64 arrays wrap mod 2^64.
+# ---------------------------------------------------------------------------
+
+_U64 = (1 << 64) - 1
+
+
+def sumtree_build(leaves, P: int):
+    """float32[2P] tree: leaves at tree[P + i] (zeros behind them), every
+    inner node n the fp32 sum tree[2n] + tree[2n+1], built bottom-up;
+    tree[1] is the root, tree[0] stays 0."""
+    import numpy as np
+
+    leaves = np.asarray(leaves, dtype=np.float32).reshape(-1)
+    assert P >= 1 and P & (P - 1) == 0 and leaves.size <= P
+    tree = np.zeros(2 * P, dtype=np.float32)
+    tree[P : P + leaves.size] = leaves
+    n = P
+    while n > 1:
+        half = n >> 1
+        tree[half:n] = tree[n : 2 * n : 2] + tree[n + 1 : 2 * n : 2]
+        n = half
+    return tree
+
+
+def sumtree_hash01(seed_u64: int, i):
+    """splitmix64 counter hash of (seed, i) -> float32 in [0, 1): the top 24
+    bits of the mixed word times 2^-24. seed is the device seed word as an
+    unsigned 64-bit value (an int64 tensor's value reduced mod 2^64)."""
+    import numpy as np
+
+    shape = np.shape(i)
+    i = np.asarray(i).astype(np.uint64).reshape(-1)
+    seed = np.full(1, int(seed_u64) & _U64, dtype=np.uint64)
+    z = seed + np.uint64(0x9E3779B97F4A7C15) * (i + np.uint64(1))
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    h = (z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+    return h.reshape(shape)
+
+
+def sumtree_bump_seed(seed: int) -> int:
+    """The LCG step of the device seed word, mod 2^64 (unsigned result)."""
+    return ((int(seed) & _U64) * 6364136223846793005
+            + 1442695040888963407) & _U64
+
+
+def sumtree_sample(tree, P: int, n_valid: int, k: int, seed: int):
+    """Stratified inverse-CDF descent, draw i of k:
+    u = (float32(i) + hash01(seed, i)) * (tree[1] / float32(k)); at each
+    level u < tree[2*node] goes left, else u -= tree[2*node] and goes right;
+    the leaf is clamped to n_valid - 1; prob = tree[P + leaf] / tree[1].
+    Returns (idx int64[k], prob float32[k])."""
+    import numpy as np
+
+    tree = np.asarray(tree, dtype=np.float32)
+    assert tree.size == 2 * P and 1 <= n_valid <= P and k >= 1
+    i = np.arange(k, dtype=np.int64)
+    total = tree[1]
+    u = (i.astype(np.float32) + sumtree_hash01(seed, i)) * (total / np.float32(k))
+    node = np.ones(k, dtype=np.int64)
+    level = 1
+    while level < P:
+        left_child = node << 1
+        lv = tree[left_child]
+        left = u < lv
+        u = np.where(left, u, u - lv)
+        node = np.where(left, left_child, left_child + 1)
+        level <<= 1
+    idx = np.minimum(node - P, n_valid - 1)
+    prob = tree[P + idx] / total
+    return idx, prob
+
+
+# ---------------------------------------------------------------------------
 # n-step return folding (actor side; APE_X/Player.py:38-51)
 # ---------------------------------------------------------------------------
 

@@ -81,7 +81,8 @@ class ReplayBase:
                 dsts = [torch.empty((idx.numel(), *c.shape[1:]),
                                     dtype=c.dtype, device=c.device)
                         for c in srcs]
-                ext.gather_rows(idx.to(torch.int64), srcs, dsts)
+                ext.gather_rows(
+                    idx.to(self.device, torch.int64).contiguous(), srcs, dsts)
                 return dict(zip(self.data.keys(), dsts))
         return {name: col.index_select(0, idx) for name, col in self.data.items()}
 
