@@ -348,6 +348,35 @@ def _resconv_ok(x: torch.Tensor, *convs: nn.Conv2d) -> bool:
     return True
 
 
+def _stem_ok(x: torch.Tensor, conv: nn.Conv2d) -> bool:
+    """Own stem-conv path (ops/hip/conv_mfma.hip conv3x3c4_*_kernel): the
+    3x3 stride-1 pad-1 conv on CUDA bf16 channels_last input, bf16
+    channels_last weight, at the one geometry the kernel has (84x84,
+    C=4 -> 16); gate DRL_OWN_STEM ('1' own kernel, '0' or unset library:
+    ops._STEM_DEFAULT, profiles/r08_stem_conv.md)."""
+    w = conv.weight
+    if tuple(w.shape[2:]) != (3, 3) or conv.stride != (1, 1) \
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) \
+            or conv.groups != 1 or conv.padding_mode != "zeros":
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        return False
+    # 8-byte pieces (one pixel's 4 channels, one tap of the weight): a
+    # weight viewed out of a flat parameter buffer may sit at any 2-byte
+    # offset
+    if w.dtype != torch.bfloat16 or w.data_ptr() % 8 or x.data_ptr() % 8 \
+            or not w.is_contiguous(memory_format=torch.channels_last):
+        return False
+    from .. import ops as _ops
+
+    if not _ops._gate("DRL_OWN_STEM", _ops._STEM_DEFAULT):
+        return False
+    return _ops.stem_conv_supported(x.shape[2], x.shape[3], w.shape[1],
+                                    w.shape[0])
+
+
 def _pool_ok(x: torch.Tensor, pool: nn.MaxPool2d) -> bool:
     """Own max-pool path (ops/hip/conv_mfma.hip maxpool3x3s2_*_kernel):
     kernel 3, stride 2, padding 1, dilation 1, floor mode; CUDA bf16
@@ -405,8 +434,11 @@ class ImpalaResNet(nn.Module):
     84x84) run through ops.fused_conv3x3 when DRL_OWN_RESCONV allows, and
     the 3x3 stride-2 pad-1 max-pools through ops.fused_maxpool3x3s2 (uint8
     tap plane, gather backward without atomics) when DRL_OWN_POOL allows.
-    The two gates are independent and are read per layer. The first conv
-    and the final ReLU+flatten stay in torch."""
+    The first conv runs through ops.fused_stem_conv3x3 (own forward and
+    ordered weight gradient: with it every parameter's gradient is
+    reproducible) when DRL_OWN_STEM=1; unset or '0' it stays in torch. The
+    three gates are independent and are read per layer. The final
+    ReLU+flatten stays in torch."""
 
     def __init__(self, cfg: Dict[str, Any]):
         super().__init__()
@@ -432,7 +464,9 @@ class ImpalaResNet(nn.Module):
             # would run it
             y = x
             for layer in self.body:
-                if isinstance(layer, nn.Conv2d) and _resconv_ok(y, layer):
+                if isinstance(layer, nn.Conv2d) and _stem_ok(y, layer):
+                    y = _ops.fused_stem_conv3x3(y, layer.weight, layer.bias)
+                elif isinstance(layer, nn.Conv2d) and _resconv_ok(y, layer):
                     # section-entry conv: no flags
                     y = _ops.fused_conv3x3(y, layer.weight, layer.bias)
                 elif isinstance(layer, nn.MaxPool2d) and _pool_ok(y, layer):

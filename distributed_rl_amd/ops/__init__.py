@@ -424,6 +424,96 @@ def fused_conv3x3(x, weight, bias, *, relu_in: bool = False,
     return torch_ref.conv3x3_res(x, weight, bias, relu_in, relu_out, residual)
 
 
+# ---------------------------------------------------------------------------
+# K2d — stem conv of the torso (3x3 pad-1, 84x84, C=4 -> 16): own forward
+# and ordered weight gradient; the input gradient (never wanted in training:
+# the frames are data) stays on the library
+# ---------------------------------------------------------------------------
+
+
+def stem_conv_supported(H, W, C, COUT) -> bool:
+    ext = hip_ext(required=False)
+    return ext is not None and bool(ext.conv3x3c4_supported(H, W, C, COUT))
+
+
+# default of DRL_OWN_STEM (read by models/base_agent.py). Off: the existing
+# tests pin the launches of the step with the environment unset. The A/B in
+# profiles/r08_stem_conv.md: medians 3.964 (gate on) vs 4.414 ms/step for
+# the parent, 4.412 with the gate unset, repeat spread at most 0.022 ms ->
+# faster by r06's rule (0.450 > 0.066). Recommended future default: on,
+# together with the edit of the tests that pin today's launches.
+_STEM_DEFAULT = False
+
+
+class _FusedStemConvFn(torch.autograd.Function):
+    """Forward on conv3x3c4_fwd_kernel. Backward: the own weight and bias
+    gradient (conv3x3c4_wrw, ordered planes, gate DRL_OWN_STEM_WRW);
+    aten.convolution_backward runs only what that leaves over — the input
+    gradient when x requires one, and everything when the gate is closed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ext = hip_ext()
+        N, _, H, W = x.shape
+        COUT = weight.shape[0]
+        out = torch.empty(
+            N, COUT, H, W, dtype=torch.bfloat16, device=x.device,
+            memory_format=torch.channels_last,
+        )
+        ext.conv3x3c4_fwd(
+            x, weight,
+            bias if bias is not None
+            else torch.empty(0, device=x.device, dtype=torch.bfloat16), out)
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, weight = ctx.saved_tensors
+        ext = hip_ext()
+        COUT = weight.shape[0]
+        if not gout.is_contiguous(memory_format=torch.channels_last):
+            gout = gout.contiguous(memory_format=torch.channels_last)
+        need_x = ctx.needs_input_grad[0]
+        need_w = ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        C, H, W = x.shape[1], x.shape[2], x.shape[3]
+        own_wrw = need_w and _gate("DRL_OWN_STEM_WRW", True) \
+            and bool(ext.conv3x3c4_wrw_supported(H, W, C, COUT))
+        gx = gw = gb = None
+        if own_wrw:
+            # (COUT, 36) in (kh, kw, c) order is the channels_last layout
+            gw = torch.empty(COUT, 3, 3, C, dtype=torch.bfloat16,
+                             device=x.device).permute(0, 3, 1, 2)
+            gb = (torch.empty(COUT, dtype=torch.bfloat16, device=x.device)
+                  if need_b else None)
+            ext.conv3x3c4_wrw(x, gout, gw,
+                              gb if need_b else torch.empty(0, device=x.device))
+        lib = [need_x, need_w and not own_wrw, need_b and not own_wrw]
+        if any(lib):
+            gx2, gw2, gb2 = torch.ops.aten.convolution_backward(
+                gout, x, weight, [COUT] if ctx.has_bias else None,
+                [1, 1], [1, 1], [1, 1], False, [0, 0], 1, lib,
+            )
+            if lib[0]:
+                gx = gx2
+            if lib[1]:
+                gw = gw2
+            if lib[2]:
+                gb = gb2
+        return gx, gw, gb
+
+
+def fused_stem_conv3x3(x, weight, bias):
+    """The torso's first conv: 3x3 stride-1 pad-1 + bias, no other fusion.
+    Device tensors must be bf16 channels_last at a geometry
+    stem_conv_supported() covers; CPU tensors take the eager reference."""
+    if _use_hip(x):
+        return _FusedStemConvFn.apply(x, weight, bias)
+    return torch_ref.conv3x3_res(x, weight, bias)
+
+
 def maxpool3x3s2_supported(H, W, C) -> bool:
     ext = hip_ext(required=False)
     return ext is not None and bool(ext.maxpool3x3s2_supported(H, W, C))

@@ -1232,8 +1232,8 @@ Conv3Launch make_conv3() {
   return l;
 }
 
-// cfg/impala_resnet.json at 84x84 (the first conv, C=4 -> K=36, stays on
-// the library)
+// cfg/impala_resnet.json at 84x84 (the first conv, C=4 -> K=36, is not in
+// this table: it has kStemLaunches and its own kernels below)
 static const Conv3Launch kConv3Launches[] = {
     // WRW_R: the fastest of 1, 2, 4 per geometry at 1344 images
     // (profiles/r06_resconv_bwd.md)
@@ -1247,6 +1247,326 @@ static const Conv3Launch kConv3Launches[] = {
 
 const Conv3Launch* find_conv3(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   for (const auto& l : kConv3Launches)
+    if (l.H == H && l.W == W && l.C == C && l.COUT == COUT) return &l;
+  return nullptr;
+}
+
+// ===========================================================================
+// Stem conv of the torso (K2d): 3x3 stride-1 pad-1 at 84x84, C=4 -> 16, the
+// one conv the kernels above cannot take (K = 36; an 8-element piece would
+// straddle two taps). One pixel's 4 channels are one 8-byte piece, so here
+// a TAP is a piece.
+//   * padded K layout [kh 0..3][kw 0..3][c 0..3] = 64 columns = two
+//     16x16x32 chunks (the second option of the two: no new builtin, the
+//     fragment maps are the ones mfma_probe already checks). Slot kw = 3 of
+//     every row and the whole row kh = 3 are pad: zeros in LDS and zeros in
+//     the im2col fragment. Lane group g = l>>4 of chunk kc holds the taps
+//     (kh = 2kc + (g>>1), kw = 2(g&1)) and (kh, kw + 1).
+//   * weights staged once per block as [cout][96]: 64 columns + 32 pad, a
+//     192-byte row stride — the kPad rule ((row bytes) % 256 in {64, 192});
+//     the bare 128-byte row would put lanes l and l+2 on the same banks.
+//     The two weight fragments are read from LDS once per wave and kept.
+//   * a piece is live iff its tap is inside the image, its slot is no pad
+//     and its row is below M; a dead piece is exact zeros and its load sits
+//     under the predicate. All live pieces of the wave's rows are issued
+//     before the first MFMA.
+//   * operands swapped as in conv3x3p1_fwd_kernel (weights as A): a lane
+//     holds 4 consecutive couts of one pixel -> one 8-byte store; the 64
+//     lanes of a 16-pixel fragment write 512 contiguous bytes.
+//   * no flags: the section-entry conv has no relu_in, relu_out or
+//     residual. Epilogue in f32: + bias, one rounding to bf16.
+// ===========================================================================
+
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+
+struct StemGeom {
+  static constexpr int C = 4, COUT = 16;
+  static constexpr int K = 9 * C;     // 36, dense (kh, kw, c)
+  static constexpr int KP = 64;       // padded [kh 4][kw 4][c 4]
+  static constexpr int KCHUNKS = KP / 32;
+  static constexpr int LDS_ROW = KP + 32;
+  static constexpr int LDS_ELEMS = COUT * LDS_ROW;
+  static constexpr int LDS_BYTES = (LDS_ELEMS + COUT) * 2;  // weights + bias
+  static_assert((LDS_ROW * 2) % 256 == 64 || (LDS_ROW * 2) % 256 == 192,
+                "LDS row stride breaks the bank-spread rule");
+  static_assert(LDS_ROW % 8 == 0, "LDS rows must stay 16-byte aligned");
+};
+
+template <int H, int W, int WAVES, int RPW>
+__global__ __launch_bounds__(WAVES * 64) void conv3x3c4_fwd_kernel(
+    const __bf16* __restrict__ in,      // (N,H,W,4) NHWC
+    const __bf16* __restrict__ weight,  // (16, 36) = (cout, kh, kw, c)
+    const __bf16* __restrict__ bias,    // (16), may be null
+    __bf16* __restrict__ out,           // (N,H,W,16)
+    int batch) {
+  using G = StemGeom;
+  constexpr int C = G::C, COUT = G::COUT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* wlds = reinterpret_cast<__bf16*>(smem);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+
+  // ---- stage weights into LDS: [cout][kh 4][kw 4][c], pad slots zero ----
+  for (int s = tid; s < COUT * 16; s += WAVES * 64) {
+    const int co = s >> 4;
+    const int slot = s & 15;
+    const int kh = slot >> 2, kw = slot & 3;
+    s16x4 v = {};
+    if (kh < 3 && kw < 3)
+      v = *reinterpret_cast<const s16x4*>(weight + co * G::K +
+                                          (kh * 3 + kw) * C);
+    *reinterpret_cast<s16x4*>(wlds + co * G::LDS_ROW + slot * C) = v;
+  }
+  __bf16* blds = wlds + G::LDS_ELEMS;
+  if (tid < COUT) blds[tid] = bias ? bias[tid] : (__bf16)0.0f;
+  __syncthreads();
+
+  const int M = batch * H * W;
+  const int row0 = (blockIdx.x * WAVES + wave) * RPW;
+  if (row0 >= M) return;
+  constexpr int RFRAG = RPW / 16;
+  const int g = lane >> 4;
+
+  // ---- every live piece of the wave's rows goes in flight first ----
+  s16x4 a[G::KCHUNKS][RFRAG][2];
+#pragma unroll
+  for (int rf = 0; rf < RFRAG; ++rf) {
+    const int arow = row0 + rf * 16 + (lane & 15);
+    const bool row_ok = arow < M;
+    const int arc = row_ok ? arow : M - 1;  // ragged tail: decode a real row
+    const int rem = arc % (H * W);
+    const int p = rem / W;
+    const int q = rem - p * W;
+    const __bf16* xrow = in + (int64_t)arc * C;  // ((n*H + p)*W + q)*C
+#pragma unroll
+    for (int kc = 0; kc < G::KCHUNKS; ++kc) {
+      const int kh = 2 * kc + (g >> 1);
+      const int dy = kh - 1;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int kw = 2 * (g & 1) + h;
+        const int dx = kw - 1;
+        a[kc][rf][h] = s16x4{};
+        const bool live = row_ok && kh < 3 && kw < 3 &&
+                          (unsigned)(p + dy) < (unsigned)H &&
+                          (unsigned)(q + dx) < (unsigned)W;
+        if (live)
+          a[kc][rf][h] = *reinterpret_cast<const s16x4*>(
+              xrow + (int64_t)(dy * W + dx) * C);
+      }
+    }
+  }
+
+  // the two weight fragments, once per wave
+  bf16x8 wa[G::KCHUNKS];
+#pragma unroll
+  for (int kc = 0; kc < G::KCHUNKS; ++kc)
+    wa[kc] = *reinterpret_cast<const bf16x8*>(
+        wlds + (lane & 15) * G::LDS_ROW + kc * 32 + g * 8);
+  const bf16x4 bv = *reinterpret_cast<const bf16x4*>(blds + g * 4);
+
+  // ---- MFMAs + epilogue: acc[r] = out[row0 + rf*16 + (l&15)][g*4 + r]
+#pragma unroll
+  for (int rf = 0; rf < RFRAG; ++rf) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kc = 0; kc < G::KCHUNKS; ++kc) {
+      const s16x8 s = __builtin_shufflevector(a[kc][rf][0], a[kc][rf][1], 0, 1,
+                                              2, 3, 4, 5, 6, 7);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          wa[kc], __builtin_bit_cast(bf16x8, s), acc, 0, 0, 0);
+    }
+    const int orow = row0 + rf * 16 + (lane & 15);
+    if (orow >= M) continue;
+    bf16x4 ov;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ov[r] = (__bf16)(acc[r] + (float)bv[r]);
+    *reinterpret_cast<bf16x4*>(out + (int64_t)orow * COUT + g * 4) = ov;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Weight gradient of the stem conv, conv3x3p1_wrw_kernel's method:
+//   gw[co][(kh,kw,c)] = sum_m gout[m][co] * im2col(x)[m][(kh,kw,c)]
+// 32-sample chunks staged plain row-major in LDS, tr_frag fragments, fp32
+// MFMA accumulate over the block's m-slice, one fp32 plane per m-slice
+// folded in a fixed order by wrw_reduce_kernel (no float atomics).
+//   * the staged x tile is [32][kh 3][kw 4][c 4] = 48 columns (+8 pad): one
+//     16-column block per kh, whose slot kw = 3 is a zero column. Wave
+//     w < 3 owns column block kh = w; wave 3 only stages.
+//   * the plane is written DENSE as (16, 36): lane column r < 12 of block
+//     kh goes to k = kh*12 + r, so n_elem = 576 = 9*64 and the fold and its
+//     bf16 store are the ones every other wrw uses.
+//   * a piece (= tap) is live iff its tap is inside the image and its row
+//     is below M; dead pieces stay zeros, their address is never formed
+//     into a load.
+//   * R consecutive chunks per pass; the next pass's pieces are loaded into
+//     registers before the current pass's MFMAs.
+// Staging: thread t stages rows (t>>3) + 32s, slots (t&7) and (t&7) + 8.
+// ---------------------------------------------------------------------------
+template <int R>
+struct StemWrw {
+  static constexpr int C = 4, COUT = 16;
+  static constexpr int K = 36;
+  static constexpr int SLOTS = 12;                // (kh, kw 0..3) per row
+  static constexpr int XIT = 2;                   // slots sj, sj + 8
+  static constexpr int XSTRIDE = SLOTS * C + kPadM;  // 56
+  static constexpr int GSTRIDE = COUT + kPadM;       // 24
+  static constexpr int GP = COUT / 8;             // gout pieces per row
+  static constexpr int ROWS = 32 * R;
+  static constexpr int GIT = (ROWS * GP + 255) / 256;
+  static constexpr int LDS_BYTES = ROWS * (XSTRIDE + GSTRIDE) * 2;
+  static_assert(XSTRIDE % 4 == 0 && GSTRIDE % 8 == 0, "aligned LDS rows");
+  static_assert(LDS_BYTES <= 64 * 1024, "dynamic LDS limit");
+};
+
+template <int H, int W, int R>
+__global__ __launch_bounds__(256) void conv3x3c4_wrw_kernel(
+    const __bf16* __restrict__ x,     // (N,H,W,4) NHWC
+    const __bf16* __restrict__ gout,  // (M, 16) = NHWC grad
+    float* __restrict__ gw_part,      // (mblocks, 576 + kPlanePad) fp32
+    int batch, int mblocks) {
+  using G = StemWrw<R>;
+  constexpr int C = G::C, COUT = G::COUT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* x_t = reinterpret_cast<__bf16*>(smem);  // [ROWS][XSTRIDE]
+  __bf16* g_t = x_t + G::ROWS * G::XSTRIDE;       // [ROWS][GSTRIDE]
+
+  const int mb = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  // wave-uniform in an SGPR: the column-block guard below must stay a
+  // scalar branch (tr16 reads need the whole wave active)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int M = batch * H * W;
+  const int n_pass = (M + G::ROWS - 1) / G::ROWS;
+
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+
+  const int srow = tid >> 3;  // staged sample row 0..31 (+ 32s)
+  const int sj = tid & 7;     // first slot of that row
+
+  s16x4 xr[R][G::XIT];
+  s16x8 gr[G::GIT];
+  auto load_pass = [&](int mc) __attribute__((always_inline)) {
+    const int m0 = mc * G::ROWS;
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      const int m = m0 + s * 32 + srow;
+      const bool valid = m < M;
+      const int mcl = valid ? m : 0;
+      const int rem = mcl % (H * W);
+      const int p = rem / W;
+      const int q = rem - p * W;
+      const __bf16* xrow = x + (int64_t)mcl * C;  // ((n*H + p)*W + q)*C
+#pragma unroll
+      for (int i = 0; i < G::XIT; ++i) {
+        xr[s][i] = s16x4{};
+        const int slot = sj + 8 * i;
+        const int kh = slot >> 2, kw = slot & 3;
+        const int dy = kh - 1, dx = kw - 1;
+        const bool live = valid && slot < G::SLOTS && kw < 3 &&
+                          (unsigned)(p + dy) < (unsigned)H &&
+                          (unsigned)(q + dx) < (unsigned)W;
+        if (live)
+          xr[s][i] = *reinterpret_cast<const s16x4*>(
+              xrow + (int64_t)(dy * W + dx) * C);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < G::GIT; ++t) {
+      const int piece = tid + 256 * t;
+      const int m = m0 + piece / G::GP;
+      gr[t] = s16x8{};
+      if (piece < G::ROWS * G::GP && m < M)
+        gr[t] = *reinterpret_cast<const s16x8*>(
+            gout + (int64_t)m * COUT + (piece % G::GP) * 8);
+    }
+  };
+
+  if (mb < n_pass) load_pass(mb);
+  for (int mc = mb; mc < n_pass; mc += mblocks) {
+    // ---- registers -> LDS (pad slots get their zeros here)
+#pragma unroll
+    for (int s = 0; s < R; ++s)
+#pragma unroll
+      for (int i = 0; i < G::XIT; ++i) {
+        const int slot = sj + 8 * i;
+        if (slot < G::SLOTS)
+          *reinterpret_cast<s16x4*>(x_t + (s * 32 + srow) * G::XSTRIDE +
+                                    slot * C) = xr[s][i];
+      }
+#pragma unroll
+    for (int t = 0; t < G::GIT; ++t) {
+      const int piece = tid + 256 * t;
+      if (piece < G::ROWS * G::GP)
+        *reinterpret_cast<s16x8*>(g_t + (piece / G::GP) * G::GSTRIDE +
+                                  (piece % G::GP) * 8) = gr[t];
+    }
+    __syncthreads();
+    if (mc + mblocks < n_pass) load_pass(mc + mblocks);
+    // ---- fragments via tr16 reads + MFMA: wave kh against the cout block
+    if (wave < 3) {
+#pragma unroll
+      for (int s = 0; s < R; ++s) {
+        const bf16x8 gf = tr_frag<G::GSTRIDE>(g_t + s * 32 * G::GSTRIDE, lane, 0);
+        const bf16x8 xf =
+            tr_frag<G::XSTRIDE>(x_t + s * 32 * G::XSTRIDE, lane, wave);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf, xf, acc, 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogue: this m-slice's partial, dense (16, 36), to its own plane
+  float* plane = gw_part + (int64_t)mb * (COUT * G::K + kPlanePad);
+  const int col = lane & 15;
+  if (wave < 3 && col < 12) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int cout = (lane >> 4) * 4 + r;
+      plane[cout * G::K + wave * 12 + col] = acc[r];
+    }
+  }
+}
+
+// the stem's own one-entry table (it does not go through kConv3Launches)
+struct StemLaunch {
+  int H, W, C, COUT;
+  void (*fwd)(const __bf16*, const __bf16*, const __bf16*, __bf16*, int);
+  int lds_bytes, waves, rpw;
+  void (*wrw)(const __bf16*, const __bf16*, float*, int, int);
+  int wrw_lds_bytes, wrw_rows;
+  void (*colsum)(const __bf16*, int64_t, float*);
+};
+
+template <int H, int W, int WAVES, int RPW, int WRW_R>
+StemLaunch make_stem() {
+  StemLaunch l{};
+  l.H = H; l.W = W; l.C = StemGeom::C; l.COUT = StemGeom::COUT;
+  l.fwd = conv3x3c4_fwd_kernel<H, W, WAVES, RPW>;
+  l.lds_bytes = StemGeom::LDS_BYTES;
+  l.waves = WAVES;
+  l.rpw = RPW;
+  l.wrw = conv3x3c4_wrw_kernel<H, W, WRW_R>;
+  l.wrw_lds_bytes = StemWrw<WRW_R>::LDS_BYTES;
+  l.wrw_rows = 32 * WRW_R;
+  l.colsum = colsum_bf16_kernel<StemGeom::COUT>;
+  return l;
+}
+
+static const StemLaunch kStemLaunches[] = {
+    // cfg/impala_resnet.json's first conv. 8 waves x 32 rows and WRW_R = 1
+    // are what the A/B and the trace of profiles/r08_stem_conv.md ran; its
+    // sweep has 4x64 at 0.91x the forward's time and WRW_R = 4 / 8 at
+    // 0.92x / 0.89x the weight gradient's, left for the change of default
+    make_stem<84, 84, 8, 32, 1>(),
+};
+
+const StemLaunch* find_stem(int64_t H, int64_t W, int64_t C, int64_t COUT) {
+  for (const auto& l : kStemLaunches)
     if (l.H == H && l.W == W && l.C == C && l.COUT == COUT) return &l;
   return nullptr;
 }
@@ -1669,23 +1989,36 @@ void launch_conv_fwd(const ConvEntry& e, const std::vector<torch::Tensor>& ins,
 // all store the same value. The m-grid, and with it the summation order and
 // the last bits of gw, follows this figure: results are reproducible on one
 // device model, not across parts with another CU count or occupancy.
-int wrw_resident_blocks(const Conv3Launch& L) {
-  constexpr int kMaxDevices = 64;
-  static std::atomic<int> cache[std::size(kConv3Launches)][kMaxDevices] = {};
+constexpr int kMaxDevices = 64;
+
+// per_dev: one table entry's kMaxDevices slots
+int resident_blocks(std::atomic<int>* per_dev, const void* fn, int lds_bytes,
+                    const char* who) {
   const int dev = at::cuda::current_device();
-  TORCH_CHECK(dev >= 0 && dev < kMaxDevices, "conv3x3p1_wrw: device index");
-  std::atomic<int>& slot = cache[&L - kConv3Launches][dev];
+  TORCH_CHECK(dev >= 0 && dev < kMaxDevices, who, ": device index");
+  std::atomic<int>& slot = per_dev[dev];
   int r = slot.load(std::memory_order_relaxed);
   if (r == 0) {
     int per_cu = 0;
     TORCH_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                    &per_cu, (const void*)L.wrw, 256, L.wrw_lds_bytes) ==
-                        hipSuccess && per_cu > 0,
-                "conv3x3p1_wrw: occupancy query failed");
+                    &per_cu, fn, 256, lds_bytes) == hipSuccess && per_cu > 0,
+                who, ": occupancy query failed");
     r = per_cu * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
     slot.store(r, std::memory_order_relaxed);
   }
   return r;
+}
+
+int wrw_resident_blocks(const Conv3Launch& L) {
+  static std::atomic<int> cache[std::size(kConv3Launches)][kMaxDevices] = {};
+  return resident_blocks(cache[&L - kConv3Launches], (const void*)L.wrw,
+                         L.wrw_lds_bytes, "conv3x3p1_wrw");
+}
+
+int wrw_resident_blocks(const StemLaunch& L) {
+  static std::atomic<int> cache[std::size(kStemLaunches)][kMaxDevices] = {};
+  return resident_blocks(cache[&L - kStemLaunches], (const void*)L.wrw,
+                         L.wrw_lds_bytes, "conv3x3c4_wrw");
 }
 
 // Ordered fold shared by every weight-grad: wrw_reduce_kernel sums the mb
@@ -2089,6 +2422,124 @@ void conv3x3p1_dgrad(torch::Tensor gout, torch::Tensor weight,
                 "conv3x3p1_dgrad mask_x"});
 }
 
+bool conv3x3c4_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
+  return find_stem(H, W, C, COUT) != nullptr;
+}
+
+bool conv3x3c4_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
+  const StemLaunch* L = find_stem(H, W, C, COUT);
+  return L && L->wrw;
+}
+
+namespace {
+// the stem entry for x (N,C,H,W) and COUT, or an error that names the
+// argument the geometry fails on
+const StemLaunch& stem_for(const torch::Tensor& x, int64_t COUT,
+                           const char* x_name, const char* cout_name) {
+  const int64_t C = x.size(1), H = x.size(2), W = x.size(3);
+  const StemLaunch* L = find_stem(H, W, C, COUT);
+  if (L) return *L;
+  bool x_known = false;
+  for (const auto& l : kStemLaunches)
+    x_known = x_known || (l.H == H && l.W == W && l.C == C);
+  TORCH_CHECK(x_known, x_name, ": no stem conv kernel for ", H, "x", W, "x", C);
+  TORCH_CHECK(false, cout_name, ": no stem conv kernel for ", H, "x", W, "x",
+              C, " -> ", COUT);
+  return kStemLaunches[0];
+}
+}  // namespace
+
+// x: (N,4,84,84) logical channels_last bf16; weight: (16,4,3,3) logical
+// channels_last bf16; bias: (16) bf16 or empty; out: (N,16,84,84) logical
+// channels_last bf16. One launch on the current stream, no allocation, no
+// sync (graph-safe).
+void conv3x3c4_fwd(torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+                   torch::Tensor out) {
+  TORCH_CHECK(x.dim() == 4 && weight.dim() == 4,
+              "conv3x3c4_fwd wants 4-D x and weight");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t COUT = weight.size(0);
+  const StemLaunch& L =
+      stem_for(x, COUT, "conv3x3c4_fwd x", "conv3x3c4_fwd weight");
+  check_nhwc(x, kBF16, N, C, H, W, "conv3x3c4_fwd x");
+  check_nhwc(weight, kBF16, COUT, C, 3, 3, "conv3x3c4_fwd weight");
+  check_nhwc(out, kBF16, N, COUT, H, W, "conv3x3c4_fwd out");
+  TORCH_CHECK(out.data_ptr() != x.data_ptr(),
+              "conv3x3c4_fwd out must not alias x");
+  // 8-byte pieces of x, weight and out
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 8 == 0,
+              "conv3x3c4_fwd x is misaligned");
+  TORCH_CHECK((uintptr_t)weight.data_ptr() % 8 == 0,
+              "conv3x3c4_fwd weight is misaligned");
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 8 == 0,
+              "conv3x3c4_fwd out is misaligned");
+  const __bf16* bias_ptr = opt_vec(bias, COUT, "conv3x3c4_fwd bias");
+  const int M = checked_rows(N * H * W, "conv3x3c4_fwd out");
+  if (M == 0) return;
+  const int rows_per_block = L.waves * L.rpw;
+  const int blocks = (M + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(L.fwd, dim3(blocks), dim3(L.waves * 64), L.lds_bytes,
+                     cur_stream(), (const __bf16*)x.data_ptr(),
+                     (const __bf16*)weight.data_ptr(), bias_ptr,
+                     (__bf16*)out.data_ptr(), (int)N);
+}
+
+// x: (N,4,84,84) and gout: (N,16,84,84) logical channels_last bf16; gw:
+// (16, 36) fp32 workspace, or the bf16 gradient itself dense in (cout, kh,
+// kw, c) order; gb: (16) of gw's dtype, or empty — conv3x3p1_wrw's
+// contracts. The only allocation is the partial planes (and the bias
+// partials of the fold).
+void conv3x3c4_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
+                   torch::Tensor gb) {
+  TORCH_CHECK(x.dim() == 4 && gout.dim() == 4,
+              "conv3x3c4_wrw wants 4-D x and gout");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t COUT = gout.size(1);
+  const StemLaunch& L =
+      stem_for(x, COUT, "conv3x3c4_wrw x", "conv3x3c4_wrw gout");
+  check_nhwc(x, kBF16, N, C, H, W, "conv3x3c4_wrw x");
+  check_nhwc(gout, kBF16, N, COUT, H, W, "conv3x3c4_wrw gout (x's batch)");
+  // 8-byte pieces of x, 16-byte pieces of gout, 16-byte stores to gw
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 8 == 0,
+              "conv3x3c4_wrw x is misaligned");
+  TORCH_CHECK((uintptr_t)gout.data_ptr() % 16 == 0,
+              "conv3x3c4_wrw gout is misaligned");
+  TORCH_CHECK(gw.defined(), "conv3x3c4_wrw gw is undefined");
+  const bool bf16_out = gw.scalar_type() == kBF16;
+  check_dev(gw, bf16_out ? kBF16 : torch::kFloat32, "conv3x3c4_wrw gw");
+  TORCH_CHECK(gw.is_contiguous() ||
+                  (gw.dim() == 4 &&
+                   gw.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              "conv3x3c4_wrw gw must be dense in (cout, kh, kw, c) order");
+  const int64_t n_elem = COUT * 9 * C;
+  TORCH_CHECK(gw.numel() == n_elem, "conv3x3c4_wrw gw must hold ", n_elem,
+              " elements, got ", gw.numel());
+  TORCH_CHECK((uintptr_t)gw.data_ptr() % 16 == 0,
+              "conv3x3c4_wrw gw is misaligned");
+  const bool bias = gb.defined() && gb.numel() > 0;
+  if (bias) check_rows(gb, gw.scalar_type(), {COUT}, "conv3x3c4_wrw gb");
+  // the last pass's row numbers run past M by less than a pass
+  const int M =
+      checked_rows(N * H * W + L.wrw_rows, "conv3x3c4_wrw x") - L.wrw_rows;
+  const int n_pass = (M + L.wrw_rows - 1) / L.wrw_rows;
+  // m-grid: conv3x3p1_wrw's three rules (a block per 8 passes, 16 MiB of
+  // planes, no more blocks than are resident at once)
+  const int64_t plane_bytes = (n_elem + kPlanePad) * 4;
+  int mb = (n_pass + 7) / 8;
+  const int mb_cap = (int)(((int64_t)16 << 20) / plane_bytes);
+  if (mb > mb_cap) mb = mb_cap;
+  const int resident = wrw_resident_blocks(L);
+  if (mb > resident) mb = resident;
+  if (mb < 1) mb = 1;
+  const auto f32 = gw.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)mb, n_elem + kPlanePad}, f32);
+  hipLaunchKernelGGL(L.wrw, dim3(mb), dim3(256), L.wrw_lds_bytes, cur_stream(),
+                     (const __bf16*)x.data_ptr(),
+                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                     (int)N, mb);
+  launch_wrw_fold(part, mb, gout, M, COUT, L.colsum, gw, gb, bias);
+}
+
 bool maxpool3x3s2_supported(int64_t H, int64_t W, int64_t C) {
   return H >= 1 && W >= 1 && C >= 16 && C % 16 == 0;
 }
@@ -2187,6 +2638,13 @@ void register_conv(pybind11::module_& m) {
   m.def("conv3x3p1_dgrad", &conv3x3p1_dgrad,
         "3x3 s1 pad-1 input-grad: weight flip + the forward kernel at the "
         "mirrored geometry (+relu_in mask in the epilogue)");
+  m.def("conv3x3c4_fwd", &conv3x3c4_fwd,
+        "MFMA 3x3 s1 pad-1 NHWC bf16 stem conv fwd (84x84, C=4 -> 16; bias)");
+  m.def("conv3x3c4_supported", &conv3x3c4_supported);
+  m.def("conv3x3c4_wrw", &conv3x3c4_wrw,
+        "MFMA stem-conv weight-grad, ordered planes; gw/gb are fp32 "
+        "workspaces or bf16 grads");
+  m.def("conv3x3c4_wrw_supported", &conv3x3c4_wrw_supported);
   m.def("maxpool3x3s2_fwd", &maxpool3x3s2_fwd,
         "NHWC bf16 max-pool 3x3 s2 pad-1 fwd; uint8 tap plane, or none when "
         "idx is empty");
