@@ -1116,8 +1116,9 @@ def impala_policy_objective(logits, actions, adv, entropy_coef,
         if stats is None:
             stats = policy_softmax_stats(logits, actions.long())
         logpa, pi, H, ent = stats
-        obj = _PolicyObjFn.apply(logits, logpa, pi, H, actions.long(),
-                                 adv.float(), entropy_coef)
+        obj = _PolicyObjFn.apply(logits, logpa, pi, H,
+                                 actions.long().contiguous(),
+                                 adv.float().contiguous(), entropy_coef)
         return obj, ent
     log_pi = torch.log_softmax(logits.float(), dim=-1)
     pi = log_pi.exp()

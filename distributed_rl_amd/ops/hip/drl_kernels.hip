@@ -233,6 +233,7 @@ __global__ void bump_seed_kernel(unsigned long long* seed) {
 //   target = r + gamma^n * Q_tgt(s', argmax_a Q_on(s',a)) * (1-done)
 //   td     = clamp(target - Q_on(s,a), -1, 1)
 //   prio   = (|td| + 1e-7)^alpha ;  loss = 0.5*mean(w * td^2)
+// The clamp passes gradient AT its bounds (raw == +-1), as torch.clamp does.
 // ---------------------------------------------------------------------------
 
 template <typename T>
@@ -270,7 +271,7 @@ __global__ void dqn_loss_fwd_kernel(
     float raw = target - q;
     float td = fminf(1.0f, fmaxf(-1.0f, raw));
     prio_out[i] = __powf(fabsf(td) + 1e-7f, alpha);
-    float in_range = (raw > -1.0f && raw < 1.0f) ? 1.0f : 0.0f;
+    float in_range = (raw >= -1.0f && raw <= 1.0f) ? 1.0f : 0.0f;
     float invB = 1.0f / B;
     grad_coef[i] = w[i] * td * in_range * invB;  // dL/dQ(s,a) = -grad_coef
     contrib = 0.5f * w[i] * td * td * invB;
@@ -510,6 +511,21 @@ int checked_count(int64_t n, const char* what) {
   TORCH_CHECK(n < (int64_t)1 << 31, what, ": too many elements");
   return (int)n;
 }
+
+// Host-side checks of the loss / target bindings, same contract as above.
+// The tensor whose sizes give the kernel its shape arguments: a contiguous
+// device tensor of `dtype` and `ndim` dimensions, none of them empty.
+void check_shape(const torch::Tensor& t, at::ScalarType dtype, int64_t ndim,
+                 const char* what) {
+  check_on(t, dtype, what);
+  TORCH_CHECK(t.dim() == ndim && t.is_contiguous() && t.numel() > 0, what,
+              " must be contiguous, ", ndim, "-D and not empty, got ",
+              t.sizes());
+}
+
+void check_positive(int64_t v, const char* what) {
+  TORCH_CHECK(v >= 1, what, " must be >= 1, got ", v);
+}
 }  // namespace
 
 void dequant(torch::Tensor src_u8, torch::Tensor dst) {
@@ -644,8 +660,24 @@ void dqn_loss_fwd(torch::Tensor q_s, torch::Tensor q_sp_on, torch::Tensor q_sp_t
                   torch::Tensor w, double gamma_n, double alpha,
                   torch::Tensor loss_out, torch::Tensor prio_out,
                   torch::Tensor grad_coef, torch::Tensor qmax_out) {
+  TORCH_CHECK(q_s.defined(), "q_s must be a device tensor");
+  const auto qt = q_s.scalar_type();
+  TORCH_CHECK(qt == torch::kFloat32 || qt == torch::kBFloat16,
+              "q_s must be Float or BFloat16, got ", qt);
+  check_shape(q_s, qt, 2, "q_s");
+  const int64_t nq = checked_count(q_s.numel(), "q_s");
   int B = (int)q_s.size(0), A = (int)q_s.size(1);
-  if (q_s.scalar_type() == torch::kBFloat16) {
+  check_vec(q_sp_on, qt, nq, q_s, "q_sp_on");
+  check_vec(q_sp_tg, qt, nq, q_s, "q_sp_tg");
+  check_vec(act, torch::kInt64, B, q_s, "act");
+  check_vec(rew, torch::kFloat32, B, q_s, "rew");
+  check_vec(done, torch::kFloat32, B, q_s, "done");
+  check_vec(w, torch::kFloat32, B, q_s, "w");
+  check_vec(loss_out, torch::kFloat32, 1, q_s, "loss_out");
+  check_vec(prio_out, torch::kFloat32, B, q_s, "prio_out");
+  check_vec(grad_coef, torch::kFloat32, B, q_s, "grad_coef");
+  check_vec(qmax_out, torch::kFloat32, 1, q_s, "qmax_out");
+  if (qt == torch::kBFloat16) {
     hipLaunchKernelGGL(dqn_loss_fwd_kernel<__bf16>, dim3(ceil_div(B, kBlock)),
                        dim3(kBlock), 0, cur_stream(),
                        (const __bf16*)q_s.data_ptr(),
@@ -670,8 +702,17 @@ void dqn_loss_fwd(torch::Tensor q_s, torch::Tensor q_sp_on, torch::Tensor q_sp_t
 
 void dqn_loss_bwd(torch::Tensor grad_coef, torch::Tensor act, torch::Tensor gout,
                   torch::Tensor grad_q) {
+  TORCH_CHECK(grad_q.defined(), "grad_q must be a device tensor");
+  const auto qt = grad_q.scalar_type();
+  TORCH_CHECK(qt == torch::kFloat32 || qt == torch::kBFloat16,
+              "grad_q must be Float or BFloat16, got ", qt);
+  check_shape(grad_q, qt, 2, "grad_q");
+  checked_count(grad_q.numel(), "grad_q");
   int B = (int)grad_q.size(0), A = (int)grad_q.size(1);
-  if (grad_q.scalar_type() == torch::kBFloat16) {
+  check_vec(grad_coef, torch::kFloat32, B, grad_q, "grad_coef");
+  check_vec(act, torch::kInt64, B, grad_q, "act");
+  check_vec(gout, torch::kFloat32, 1, grad_q, "gout");
+  if (qt == torch::kBFloat16) {
     hipLaunchKernelGGL(dqn_loss_bwd_kernel<__bf16>,
                        dim3(ceil_div((int64_t)B * A, kBlock)), dim3(kBlock), 0,
                        cur_stream(), grad_coef.data_ptr<float>(),
@@ -687,14 +728,18 @@ void dqn_loss_bwd(torch::Tensor grad_coef, torch::Tensor act, torch::Tensor gout
 }
 
 void value_rescale(torch::Tensor x, torch::Tensor y, double eps) {
+  check_shape(x, torch::kFloat32, x.dim(), "x");
   int64_t n = x.numel();
+  check_vec(y, torch::kFloat32, n, x, "y");
   hipLaunchKernelGGL(value_rescale_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                      cur_stream(), x.data_ptr<float>(), y.data_ptr<float>(), n,
                      (float)eps);
 }
 
 void inv_value_rescale(torch::Tensor x, torch::Tensor y, double eps) {
+  check_shape(x, torch::kFloat32, x.dim(), "x");
   int64_t n = x.numel();
+  check_vec(y, torch::kFloat32, n, x, "y");
   hipLaunchKernelGGL(inv_value_rescale_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                      cur_stream(), x.data_ptr<float>(), y.data_ptr<float>(), n,
                      (float)eps);
@@ -702,7 +747,10 @@ void inv_value_rescale(torch::Tensor x, torch::Tensor y, double eps) {
 
 void seq_priority(torch::Tensor td_abs, double eta, double alpha,
                   torch::Tensor out) {
+  check_shape(td_abs, torch::kFloat32, 2, "td_abs");
+  checked_count(td_abs.numel(), "td_abs");
   int T = (int)td_abs.size(0), B = (int)td_abs.size(1);
+  check_vec(out, torch::kFloat32, B, td_abs, "out");
   hipLaunchKernelGGL(seq_priority_kernel, dim3(ceil_div(B, kBlock)), dim3(kBlock), 0,
                      cur_stream(), td_abs.data_ptr<float>(), T, B, (float)eta,
                      (float)alpha, out.data_ptr<float>());
@@ -712,7 +760,17 @@ void vtrace(torch::Tensor b_logp, torch::Tensor t_logp, torch::Tensor rew,
             torch::Tensor values, torch::Tensor boot, torch::Tensor not_done,
             double gamma, double rho_bar, double c_bar, double lam,
             torch::Tensor vs, torch::Tensor pg_adv, torch::Tensor rho_out) {
+  check_shape(rew, torch::kFloat32, 2, "rew");
+  const int64_t n = checked_count(rew.numel(), "rew");
   int T = (int)rew.size(0), B = (int)rew.size(1);
+  check_vec(b_logp, torch::kFloat32, n, rew, "b_logp");
+  check_vec(t_logp, torch::kFloat32, n, rew, "t_logp");
+  check_vec(values, torch::kFloat32, n, rew, "values");
+  check_vec(boot, torch::kFloat32, B, rew, "boot");
+  check_vec(not_done, torch::kFloat32, B, rew, "not_done");
+  check_vec(vs, torch::kFloat32, n, rew, "vs");
+  check_vec(pg_adv, torch::kFloat32, n, rew, "pg_adv");
+  check_vec(rho_out, torch::kFloat32, n, rew, "rho_out");
   hipLaunchKernelGGL(vtrace_kernel, dim3(ceil_div(B, kBlock)), dim3(kBlock), 0,
                      cur_stream(), b_logp.data_ptr<float>(),
                      t_logp.data_ptr<float>(), rew.data_ptr<float>(),
@@ -727,12 +785,16 @@ void vtrace_bt(torch::Tensor mu, torch::Tensor t_logp, torch::Tensor rew,
                torch::Tensor values, torch::Tensor boot, torch::Tensor not_done,
                double gamma, double rho_bar, double c_bar, double lam,
                torch::Tensor vs, torch::Tensor pg_adv) {
+  check_shape(rew, torch::kFloat32, 2, "rew");
+  const int64_t n = checked_count(rew.numel(), "rew");
   int B = (int)rew.size(0), T = (int)rew.size(1);
-  for (auto* t : {&mu, &t_logp, &values, &vs, &pg_adv}) {
-    DRL_CHECK_CONTIG((*t));
-    TORCH_CHECK(t->numel() == (int64_t)B * T, "vtrace_bt shape mismatch");
-  }
-  TORCH_CHECK(boot.numel() == B && not_done.numel() == B);
+  check_vec(mu, torch::kFloat32, n, rew, "mu");
+  check_vec(t_logp, torch::kFloat32, n, rew, "t_logp");
+  check_vec(values, torch::kFloat32, n, rew, "values");
+  check_vec(boot, torch::kFloat32, B, rew, "boot");
+  check_vec(not_done, torch::kFloat32, B, rew, "not_done");
+  check_vec(vs, torch::kFloat32, n, rew, "vs");
+  check_vec(pg_adv, torch::kFloat32, n, rew, "pg_adv");
   hipLaunchKernelGGL(vtrace_bt_kernel, dim3(ceil_div(B, kBlock)), dim3(kBlock),
                      0, cur_stream(), mu.data_ptr<float>(),
                      t_logp.data_ptr<float>(), rew.data_ptr<float>(),
@@ -743,6 +805,11 @@ void vtrace_bt(torch::Tensor mu, torch::Tensor t_logp, torch::Tensor rew,
 }
 
 void grad_clip(torch::Tensor flat, double max_norm, torch::Tensor sqsum_buf) {
+  check_shape(flat, torch::kFloat32, flat.dim(), "flat");
+  // sq_sum_kernel reads the buffer as float4
+  TORCH_CHECK(((uintptr_t)flat.data_ptr() & 15) == 0,
+              "flat must be 16-byte aligned");
+  check_vec(sqsum_buf, torch::kFloat32, 1, flat, "sqsum_buf");
   int64_t n = flat.numel();
   hipLaunchKernelGGL(sq_sum_kernel, dim3(grid_for(n, 8)), dim3(kBlock), 0,
                      cur_stream(), flat.data_ptr<float>(), n,
@@ -1026,14 +1093,22 @@ __global__ void dueling_bwd_kernel(const float* __restrict__ g, int B, int A,
 }  // namespace
 
 void dueling_fwd(torch::Tensor adv, torch::Tensor val, torch::Tensor out) {
+  check_shape(adv, torch::kFloat32, 2, "adv");
+  const int64_t n = checked_count(adv.numel(), "adv");
   int B = (int)adv.size(0), A = (int)adv.size(1);
+  check_vec(val, torch::kFloat32, B, adv, "val");
+  check_vec(out, torch::kFloat32, n, adv, "out");
   hipLaunchKernelGGL(dueling_fwd_kernel, dim3(ceil_div(B, kBlock)), dim3(kBlock),
                      0, cur_stream(), adv.data_ptr<float>(),
                      val.data_ptr<float>(), B, A, out.data_ptr<float>());
 }
 
 void dueling_bwd(torch::Tensor g, torch::Tensor gadv, torch::Tensor gval) {
+  check_shape(g, torch::kFloat32, 2, "g");
+  const int64_t n = checked_count(g.numel(), "g");
   int B = (int)g.size(0), A = (int)g.size(1);
+  check_vec(gadv, torch::kFloat32, n, g, "gadv");
+  check_vec(gval, torch::kFloat32, B, g, "gval");
   hipLaunchKernelGGL(dueling_bwd_kernel, dim3(ceil_div(B, kBlock)), dim3(kBlock),
                      0, cur_stream(), g.data_ptr<float>(), B, A,
                      gadv.data_ptr<float>(), gval.data_ptr<float>());
@@ -1287,7 +1362,16 @@ void policy_loss_fwd(torch::Tensor logits, torch::Tensor act, torch::Tensor adv,
                      double er, torch::Tensor obj_out, torch::Tensor ent_out,
                      torch::Tensor logpa_out, torch::Tensor pi_save,
                      torch::Tensor H_save) {
+  check_shape(logits, torch::kFloat32, 2, "logits");
+  const int64_t n = checked_count(logits.numel(), "logits");
   int N = (int)logits.size(0), A = (int)logits.size(1);
+  check_vec(act, torch::kInt64, N, logits, "act");
+  check_vec(adv, torch::kFloat32, N, logits, "adv");
+  check_vec(obj_out, torch::kFloat32, 1, logits, "obj_out");
+  check_vec(ent_out, torch::kFloat32, 1, logits, "ent_out");
+  check_vec(logpa_out, torch::kFloat32, N, logits, "logpa_out");
+  check_vec(pi_save, torch::kFloat32, n, logits, "pi_save");
+  check_vec(H_save, torch::kFloat32, N, logits, "H_save");
   hipLaunchKernelGGL(policy_loss_fwd_kernel, dim3(ceil_div(N, kBlock)),
                      dim3(kBlock), 0, cur_stream(), logits.data_ptr<float>(),
                      act.data_ptr<int64_t>(), adv.data_ptr<float>(), N, A,
@@ -1299,7 +1383,14 @@ void policy_loss_fwd(torch::Tensor logits, torch::Tensor act, torch::Tensor adv,
 void policy_loss_bwd(torch::Tensor pi_save, torch::Tensor H_save,
                      torch::Tensor act, torch::Tensor adv, torch::Tensor gout,
                      double er, double gsign, torch::Tensor dlogits) {
+  check_shape(pi_save, torch::kFloat32, 2, "pi_save");
+  const int64_t n = checked_count(pi_save.numel(), "pi_save");
   int N = (int)pi_save.size(0), A = (int)pi_save.size(1);
+  check_vec(H_save, torch::kFloat32, N, pi_save, "H_save");
+  check_vec(act, torch::kInt64, N, pi_save, "act");
+  check_vec(adv, torch::kFloat32, N, pi_save, "adv");
+  check_vec(gout, torch::kFloat32, 1, pi_save, "gout");
+  check_vec(dlogits, torch::kFloat32, n, pi_save, "dlogits");
   hipLaunchKernelGGL(policy_loss_bwd_kernel,
                      dim3(ceil_div((int64_t)N * A, kBlock)), dim3(kBlock), 0,
                      cur_stream(), pi_save.data_ptr<float>(),
@@ -1312,10 +1403,15 @@ void impala_loss_fwd(torch::Tensor logpa, torch::Tensor adv,
                      torch::Tensor mean_H, torch::Tensor v, torch::Tensor vs,
                      double er, torch::Tensor loss_out, torch::Tensor obj_out,
                      torch::Tensor critic_out) {
+  check_shape(logpa, torch::kFloat32, logpa.dim(), "logpa");
   int64_t n = logpa.numel();
-  TORCH_CHECK(adv.numel() == n && v.numel() == n && vs.numel() == n,
-              "impala_loss_fwd length mismatch");
-  for (auto* t : {&logpa, &adv, &v, &vs}) DRL_CHECK_CONTIG((*t));
+  check_vec(adv, torch::kFloat32, n, logpa, "adv");
+  check_vec(mean_H, torch::kFloat32, 1, logpa, "mean_H");
+  check_vec(v, torch::kFloat32, n, logpa, "v");
+  check_vec(vs, torch::kFloat32, n, logpa, "vs");
+  check_vec(loss_out, torch::kFloat32, 1, logpa, "loss_out");
+  check_vec(obj_out, torch::kFloat32, 1, logpa, "obj_out");
+  check_vec(critic_out, torch::kFloat32, 1, logpa, "critic_out");
   hipLaunchKernelGGL(impala_loss_fwd_kernel, dim3(1), dim3(kBlock), 0,
                      cur_stream(), logpa.data_ptr<float>(),
                      adv.data_ptr<float>(), mean_H.data_ptr<float>(),
@@ -1328,11 +1424,23 @@ void impala_out_bwd(torch::Tensor pi_save, torch::Tensor H_save,
                     torch::Tensor act, torch::Tensor adv, torch::Tensor v,
                     torch::Tensor vs, torch::Tensor gloss, int64_t B,
                     int64_t T, int64_t A, double er, torch::Tensor dout) {
-  int64_t total = B * (T + 1) * (A + 1);
-  TORCH_CHECK(dout.numel() == total && dout.is_contiguous(),
-              "impala_out_bwd dout shape mismatch");
-  TORCH_CHECK(pi_save.numel() == B * T * A && v.numel() == B * T &&
-              vs.numel() == B * T && act.numel() == B * T);
+  check_positive(B, "B");
+  check_positive(T, "T");
+  check_positive(A, "A");
+  TORCH_CHECK(B < (1 << 30) && T < (1 << 30) && A < (1 << 30),
+              "B, T, A: too many elements");
+  TORCH_CHECK(B * (T + 1) < ((int64_t)1 << 31),
+              "B, T: too many elements");
+  int64_t total = checked_count(B * (T + 1) * (A + 1), "dout");
+  check_shape(pi_save, torch::kFloat32, pi_save.dim(), "pi_save");
+  check_vec(pi_save, torch::kFloat32, B * T * A, pi_save, "pi_save");
+  check_vec(H_save, torch::kFloat32, B * T, pi_save, "H_save");
+  check_vec(act, torch::kInt64, B * T, pi_save, "act");
+  check_vec(adv, torch::kFloat32, B * T, pi_save, "adv");
+  check_vec(v, torch::kFloat32, B * T, pi_save, "v");
+  check_vec(vs, torch::kFloat32, B * T, pi_save, "vs");
+  check_vec(gloss, torch::kFloat32, 1, pi_save, "gloss");
+  check_vec(dout, torch::kFloat32, total, pi_save, "dout");
   hipLaunchKernelGGL(impala_out_bwd_kernel, dim3(grid_for(total, 2)),
                      dim3(kBlock), 0, cur_stream(), pi_save.data_ptr<float>(),
                      H_save.data_ptr<float>(), act.data_ptr<int64_t>(),
@@ -2022,7 +2130,7 @@ __global__ void dueling_dqn_loss_fwd_kernel(
     float raw = target - q;
     float td = fminf(1.0f, fmaxf(-1.0f, raw));
     prio_out[i] = __powf(fabsf(td) + 1e-7f, alpha);
-    float in_range = (raw > -1.0f && raw < 1.0f) ? 1.0f : 0.0f;
+    float in_range = (raw >= -1.0f && raw <= 1.0f) ? 1.0f : 0.0f;
     float invB = 1.0f / B;
     grad_coef[i] = w[i] * td * in_range * invB;  // dL/dQ(s,a) = -grad_coef
     contrib = 0.5f * w[i] * td * td * invB;
@@ -2061,7 +2169,27 @@ void dueling_dqn_loss_fwd(torch::Tensor adv_s, torch::Tensor val_s,
                           double alpha, torch::Tensor loss_out,
                           torch::Tensor prio_out, torch::Tensor grad_coef,
                           torch::Tensor qmax_out) {
+  TORCH_CHECK(adv_s.defined(), "adv_s must be a device tensor");
+  const auto qt = adv_s.scalar_type();
+  TORCH_CHECK(qt == torch::kFloat32 || qt == torch::kBFloat16 ||
+                  qt == torch::kFloat16,
+              "adv_s must be Float, BFloat16 or Half, got ", qt);
+  check_shape(adv_s, qt, 2, "adv_s");
+  const int64_t nq = checked_count(adv_s.numel(), "adv_s");
   int B = (int)adv_s.size(0), A = (int)adv_s.size(1);
+  check_vec(val_s, qt, B, adv_s, "val_s");
+  check_vec(adv_on, qt, nq, adv_s, "adv_on");
+  check_vec(val_on, qt, B, adv_s, "val_on");
+  check_vec(adv_tg, qt, nq, adv_s, "adv_tg");
+  check_vec(val_tg, qt, B, adv_s, "val_tg");
+  check_vec(act, torch::kInt64, B, adv_s, "act");
+  check_vec(rew, torch::kFloat32, B, adv_s, "rew");
+  check_vec(done, torch::kFloat32, B, adv_s, "done");
+  check_vec(w, torch::kFloat32, B, adv_s, "w");
+  check_vec(loss_out, torch::kFloat32, 1, adv_s, "loss_out");
+  check_vec(prio_out, torch::kFloat32, B, adv_s, "prio_out");
+  check_vec(grad_coef, torch::kFloat32, B, adv_s, "grad_coef");
+  check_vec(qmax_out, torch::kFloat32, 1, adv_s, "qmax_out");
   dim3 grid(ceil_div(B, kBlock)), blk(kBlock);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::BFloat16, at::ScalarType::Half, adv_s.scalar_type(),
@@ -2082,7 +2210,18 @@ void dueling_dqn_loss_fwd(torch::Tensor adv_s, torch::Tensor val_s,
 void dueling_dqn_loss_bwd(torch::Tensor grad_coef, torch::Tensor act,
                           torch::Tensor gout, torch::Tensor g_adv,
                           torch::Tensor g_val) {
+  TORCH_CHECK(g_adv.defined(), "g_adv must be a device tensor");
+  const auto qt = g_adv.scalar_type();
+  TORCH_CHECK(qt == torch::kFloat32 || qt == torch::kBFloat16 ||
+                  qt == torch::kFloat16,
+              "g_adv must be Float, BFloat16 or Half, got ", qt);
+  check_shape(g_adv, qt, 2, "g_adv");
+  checked_count(g_adv.numel(), "g_adv");
   int B = (int)g_adv.size(0), A = (int)g_adv.size(1);
+  check_vec(grad_coef, torch::kFloat32, B, g_adv, "grad_coef");
+  check_vec(act, torch::kInt64, B, g_adv, "act");
+  check_vec(gout, torch::kFloat32, 1, g_adv, "gout");
+  check_vec(g_val, qt, B, g_adv, "g_val");
   dim3 grid(ceil_div((int64_t)B * A, kBlock)), blk(kBlock);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::BFloat16, at::ScalarType::Half, g_adv.scalar_type(),
@@ -2609,7 +2748,7 @@ __global__ __launch_bounds__(256) void dueling_q_loss_fwd_kernel(
     const float raw = target - q;
     const float td = fminf(1.0f, fmaxf(-1.0f, raw));
     prio_out[b] = __powf(fabsf(td) + 1e-7f, alpha);
-    const float in_range = (raw > -1.0f && raw < 1.0f) ? 1.0f : 0.0f;
+    const float in_range = (raw >= -1.0f && raw <= 1.0f) ? 1.0f : 0.0f;
     const float invB = 1.0f / B;
     grad_coef[b] = w[b] * td * in_range * invB;
     atomicAdd(loss_out, 0.5f * w[b] * td * td * invB);
@@ -2719,8 +2858,34 @@ void dueling_q_loss_fwd(torch::Tensor h_s, torch::Tensor h_on,
                         double gamma_n, double alpha, torch::Tensor loss_out,
                         torch::Tensor prio_out, torch::Tensor grad_coef,
                         torch::Tensor qmax_out, bool pre_act) {
+  constexpr auto bf = torch::kBFloat16;
+  check_shape(h_s, bf, 2, "h_s");
+  TORCH_CHECK(h_s.size(1) == 1024, "h_s must be (B, 1024), got ",
+              h_s.sizes());
+  const int64_t nh = checked_count(h_s.numel(), "h_s");
   int B = (int)h_s.size(0);
-  TORCH_CHECK(h_s.size(1) == 1024 && wa.size(0) == 6, "geometry: HH=512 A=6");
+  check_vec(h_on, bf, nh, h_s, "h_on");
+  check_vec(h_tg, bf, nh, h_s, "h_tg");
+  check_vec(wa, bf, 6 * 512, h_s, "wa");
+  TORCH_CHECK(wa.dim() == 2 && wa.size(0) == 6, "wa must be (6, 512), got ",
+              wa.sizes());
+  check_vec(ba, bf, 6, h_s, "ba");
+  check_vec(wv, bf, 512, h_s, "wv");
+  check_vec(bv, bf, 1, h_s, "bv");
+  check_vec(wa_t, bf, 6 * 512, h_s, "wa_t");
+  TORCH_CHECK(wa_t.dim() == 2 && wa_t.size(0) == 6,
+              "wa_t must be (6, 512), got ", wa_t.sizes());
+  check_vec(ba_t, bf, 6, h_s, "ba_t");
+  check_vec(wv_t, bf, 512, h_s, "wv_t");
+  check_vec(bv_t, bf, 1, h_s, "bv_t");
+  check_vec(act, torch::kInt64, B, h_s, "act");
+  check_vec(rew, torch::kFloat32, B, h_s, "rew");
+  check_vec(done, torch::kFloat32, B, h_s, "done");
+  check_vec(w, torch::kFloat32, B, h_s, "w");
+  check_vec(loss_out, torch::kFloat32, 1, h_s, "loss_out");
+  check_vec(prio_out, torch::kFloat32, B, h_s, "prio_out");
+  check_vec(grad_coef, torch::kFloat32, B, h_s, "grad_coef");
+  check_vec(qmax_out, torch::kFloat32, 1, h_s, "qmax_out");
   hipLaunchKernelGGL((pre_act ? dueling_q_loss_fwd_kernel<512, 6, true>
                               : dueling_q_loss_fwd_kernel<512, 6, false>),
                      dim3((B + 3) / 4), dim3(256), 0, cur_stream(),
@@ -2744,8 +2909,24 @@ void dueling_q_loss_bwd(torch::Tensor grad_coef, torch::Tensor act,
                         torch::Tensor h_s, torch::Tensor dh, torch::Tensor dwa,
                         torch::Tensor dba, torch::Tensor dwv,
                         torch::Tensor dbv, bool pre_act) {
+  constexpr auto bf = torch::kBFloat16;
+  check_shape(h_s, bf, 2, "h_s");
+  TORCH_CHECK(h_s.size(1) == 1024, "h_s must be (B, 1024), got ",
+              h_s.sizes());
+  const int64_t nh = checked_count(h_s.numel(), "h_s");
   int B = (int)h_s.size(0);
-  TORCH_CHECK(h_s.numel() == (int64_t)B * 1024 && dh.numel() == h_s.numel());
+  check_vec(grad_coef, torch::kFloat32, B, h_s, "grad_coef");
+  check_vec(act, torch::kInt64, B, h_s, "act");
+  check_vec(gout, torch::kFloat32, 1, h_s, "gout");
+  check_vec(wa, bf, 6 * 512, h_s, "wa");
+  TORCH_CHECK(wa.dim() == 2 && wa.size(0) == 6, "wa must be (6, 512), got ",
+              wa.sizes());
+  check_vec(wv, bf, 512, h_s, "wv");
+  check_vec(dh, bf, nh, h_s, "dh");
+  check_vec(dwa, bf, 6 * 512, h_s, "dwa");
+  check_vec(dba, bf, 6, h_s, "dba");
+  check_vec(dwv, bf, 512, h_s, "dwv");
+  check_vec(dbv, bf, 1, h_s, "dbv");
   hipLaunchKernelGGL((pre_act ? dueling_q_loss_bwd_dh_kernel<512, 6, true>
                               : dueling_q_loss_bwd_dh_kernel<512, 6, false>),
                      dim3(ceil_div((int64_t)B * 1024, kBlock)), dim3(kBlock),
@@ -2908,8 +3089,21 @@ void r2d2_loss_fwd(torch::Tensor q_train, torch::Tensor q_tgt,
                    torch::Tensor act, torch::Tensor rew, torch::Tensor done,
                    torch::Tensor w, int64_t m, int64_t n_step, double gamma,
                    bool rescale, torch::Tensor td_out, torch::Tensor stats) {
+  check_shape(q_tgt, torch::kFloat32, 3, "q_tgt");
+  checked_count(q_tgt.numel(), "q_tgt");
   int T = (int)q_tgt.size(0), B = (int)q_tgt.size(1), A = (int)q_tgt.size(2);
+  TORCH_CHECK(m >= 0 && m <= T - 2, "m must be in [0, T-2], got ", m,
+              " with T = ", T);
+  check_positive(n_step, "n_step");
   const int W = T - 1 - (int)m;
+  check_vec(q_train, torch::kFloat32, (int64_t)(T - m) * B * A, q_tgt,
+            "q_train");
+  check_vec(act, torch::kInt32, (int64_t)T * B, q_tgt, "act");
+  check_vec(rew, torch::kFloat32, (int64_t)T * B, q_tgt, "rew");
+  check_vec(done, torch::kFloat32, B, q_tgt, "done");
+  check_vec(w, torch::kFloat32, B, q_tgt, "w");
+  check_vec(td_out, torch::kFloat32, (int64_t)W * B, q_tgt, "td_out");
+  check_vec(stats, torch::kFloat32, 3, q_tgt, "stats");
   hipLaunchKernelGGL(r2d2_loss_fwd_kernel,
                      dim3(ceil_div((int64_t)W * B, kBlock)), dim3(kBlock), 0,
                      cur_stream(), q_train.data_ptr<float>(),
@@ -2922,7 +3116,10 @@ void r2d2_loss_fwd(torch::Tensor q_train, torch::Tensor q_tgt,
 
 void r2d2_prio(torch::Tensor td, double alpha, double eta,
                torch::Tensor prio) {
+  check_shape(td, torch::kFloat32, 2, "td");
+  checked_count(td.numel(), "td");
   int W = (int)td.size(0), B = (int)td.size(1);
+  check_vec(prio, torch::kFloat32, B, td, "prio");
   hipLaunchKernelGGL(r2d2_prio_kernel, dim3(ceil_div(B, 4)), dim3(256), 0,
                      cur_stream(), td.data_ptr<float>(), W, B, (float)alpha,
                      (float)eta, prio.data_ptr<float>());
@@ -2931,7 +3128,18 @@ void r2d2_prio(torch::Tensor td, double alpha, double eta,
 void r2d2_loss_bwd(torch::Tensor td, torch::Tensor act, torch::Tensor w,
                    torch::Tensor gout, int64_t T, int64_t m,
                    torch::Tensor dq) {
+  check_shape(td, torch::kFloat32, 2, "td");
+  check_shape(dq, torch::kFloat32, 3, "dq");
+  checked_count(dq.numel(), "dq");
   int B = (int)td.size(1), A = (int)dq.size(2);
+  TORCH_CHECK(m >= 0 && T - 1 - m == td.size(0),
+              "td must have T - 1 - m rows, got ", td.sizes(), " with T = ", T,
+              ", m = ", m);
+  TORCH_CHECK(dq.size(0) == T - m && dq.size(1) == B,
+              "dq must be (T - m, B, A), got ", dq.sizes());
+  check_vec(act, torch::kInt32, T * B, td, "act");
+  check_vec(w, torch::kFloat32, B, td, "w");
+  check_vec(gout, torch::kFloat32, 1, td, "gout");
   const int64_t total = (int64_t)(T - m) * B * A;
   hipLaunchKernelGGL(r2d2_loss_bwd_kernel, dim3(ceil_div(total, kBlock)),
                      dim3(kBlock), 0, cur_stream(), td.data_ptr<float>(),

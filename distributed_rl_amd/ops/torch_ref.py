@@ -1,4 +1,5 @@
-"""Pure-PyTorch (fp32, eager) reference implementations of every fused HIP op.
+"""Pure-PyTorch (eager) reference implementations of every fused HIP op:
+fp32 by default, fp64 when fed fp64 (the loss / target oracles are).
 
 These are the numerics oracles the HIP kernels (distributed_rl_amd/ops/hip/*)
 are unit-tested against, and the CPU execution path (no GPU present).
@@ -237,6 +238,129 @@ def impala_loss(
     critic_loss = 0.5 * torch.nn.functional.mse_loss(values_pred, vs.detach())
     total = -obj_actor + critic_coef * critic_loss
     return total, obj_actor, critic_loss, entropy
+
+
+# ---------------------------------------------------------------------------
+# fp64 oracles of the fused sequence / head losses. Written from the
+# formulas, not from the kernels: plain loops and autograd, no ops.* calls.
+# ---------------------------------------------------------------------------
+
+
+def r2d2_sequence_loss_ref(q_train, q_tgt, actions, rewards, done, weights,
+                           burn_in: int, n_step: int, gamma: float,
+                           alpha: float, eta: float, use_rescaling: bool):
+    """R2D2 target / loss / priority over one batch of sequences, in fp64.
+
+    q_train (T-m, B, A) online rows from the burn-in m on, q_tgt (T, B, A),
+    actions / rewards (T, B), done / weights (B,). For every window step
+    t in [m, T-1): n = min(n_step, T-1-t), a* = argmax_a q_online[t+n],
+    G = sum_{k<n} gamma^k r_{t+k} + gamma^n h^-1(q_tgt[t+n, a*]), the
+    bootstrap masked by (1 - done) only where t+n == T-1, and
+    td = h(G) - q_online[t, a_t].
+
+    Returns dict(td (W, B), loss, prio (B,), value, td_abs, dq_train), with
+    dq_train = d loss / d q_train in closed form (the target is constant).
+    """
+    import math
+
+    T, B, A = q_tgt.shape
+    m = int(burn_in)
+    W = T - 1 - m
+    qo = q_train.double().tolist()
+    qt = q_tgt.double().tolist()
+    act = actions.long().tolist()
+    rew = rewards.double().tolist()
+    dn = done.double().tolist()
+    wt = weights.double().tolist()
+    eps = _RESCALE_EPS
+
+    def h(x):
+        return math.copysign(math.sqrt(abs(x) + 1.0) - 1.0, x) + eps * x
+
+    def h_inv(x):
+        r = (math.sqrt(1.0 + 4.0 * eps * (abs(x) + 1.0 + eps)) - 1.0) / (2.0 * eps)
+        return math.copysign(r * r - 1.0, x)
+
+    td = torch.zeros(W, B, dtype=torch.float64)
+    dq = torch.zeros(T - m, B, A, dtype=torch.float64)
+    loss = value = 0.0
+    for ti in range(W):
+        t = m + ti
+        n = min(n_step, T - 1 - t)
+        tn = t + n
+        for b in range(B):
+            ret = sum(gamma ** k * rew[t + k][b] for k in range(n))
+            row = qo[tn - m][b]
+            a_star = max(range(A), key=lambda a: (row[a], -a))  # earliest max
+            boot = qt[tn][b][a_star]
+            if use_rescaling:
+                boot = h_inv(boot)
+            if tn == T - 1:
+                boot *= 1.0 - dn[b]
+            G = ret + gamma ** n * boot
+            if use_rescaling:
+                G = h(G)
+            q_taken = qo[ti][b][act[t][b]]
+            d = G - q_taken
+            td[ti, b] = d
+            loss += 0.5 * wt[b] * d * d
+            value += q_taken
+            dq[ti, b, act[t][b]] = -wt[b] * d / (B * W)
+    td_abs = td.abs()
+    prio = (eta * td_abs.max(dim=0).values
+            + (1.0 - eta) * td_abs.mean(dim=0)) ** alpha
+    return dict(td=td, loss=torch.tensor(loss / (B * W), dtype=torch.float64),
+                prio=prio,
+                value=torch.tensor(value / (B * W), dtype=torch.float64),
+                td_abs=td_abs.mean(), dq_train=dq)
+
+
+def dueling_q_head_loss_ref(h_s, wa, ba, wv, bv, h_on, h_tg, wa_t, ba_t, wv_t,
+                            bv_t, actions, rewards, dones, weights,
+                            gamma: float, n_step: int, alpha: float,
+                            pre_act: bool = False, gout: float = 1.0,
+                            dtype: torch.dtype = torch.float64):
+    """Heads on the [adv | val] halves of the hidden rows, optional ReLU,
+    dueling, n-step double-DQN loss, all in fp64; gradients of gout * loss
+    for (h_s, wa, ba, wv, bv) by autograd. ``dtype`` = fp32 runs the same
+    formula in fp32 (a scale for a kernel's error, not a reference).
+
+    Returns dict(loss, prio, qmean, a_star, raw, td, q_on, dh, dwa, dba, dwv,
+    dbv); raw is the unclipped TD error and q_on the online Q(s', .) rows
+    (what decides a*)."""
+    HH = wa.shape[1]
+    leaves = [t.detach().to(dtype).clone().requires_grad_(True)
+              for t in (h_s, wa, ba, wv.reshape(1, -1), bv.reshape(1))]
+    hs, wa_, ba_, wv_, bv_ = leaves
+    c = [t.detach().to(dtype) for t in (h_on, h_tg, wa_t, ba_t,
+                                        wv_t.reshape(1, -1), bv_t.reshape(1))]
+    rewards, dones, weights = (t.to(dtype) for t in (rewards, dones, weights))
+    hon, htg, wat, bat, wvt, bvt = c
+
+    def q_of(h, w_a, b_a, w_v, b_v):
+        if pre_act:
+            h = torch.relu(h)
+        adv = h[:, :HH] @ w_a.t() + b_a
+        val = h[:, HH:] @ w_v.t() + b_v
+        return adv - adv.mean(dim=1, keepdim=True) + val
+
+    q_s = q_of(hs, wa_, ba_, wv_, bv_)
+    with torch.no_grad():
+        q_on = q_of(hon, wa_, ba_, wv_, bv_)
+        q_tg = q_of(htg, wat, bat, wvt, bvt)
+        a_star = q_on.argmax(dim=1)
+        target = rewards + gamma ** n_step * q_tg.gather(
+            1, a_star.unsqueeze(1)).squeeze(1) * (1.0 - dones)
+    q_sa = q_s.gather(1, actions.long().unsqueeze(1)).squeeze(1)
+    raw = target - q_sa
+    td = raw.clamp(-1.0, 1.0)
+    loss = 0.5 * (weights * td.pow(2)).mean()
+    grads = torch.autograd.grad(loss * gout, leaves)
+    return dict(loss=loss.detach(), prio=(td.detach().abs() + 1e-7) ** alpha,
+                qmean=q_s.detach().max(dim=1).values.mean(), a_star=a_star,
+                raw=raw.detach(), td=td.detach(), q_on=q_on,
+                dh=grads[0], dwa=grads[1], dba=grads[2],
+                dwv=grads[3].reshape(wv.shape), dbv=grads[4].reshape(bv.shape))
 
 
 # ---------------------------------------------------------------------------
