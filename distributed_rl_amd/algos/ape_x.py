@@ -560,7 +560,10 @@ class ApexLearner(LearnerBase):
                 with_value_stat=True,
             )
         if self.mp is not None:
-            self.mp.direct_grads(loss, getattr(self, "_direct_list", None))
+            # the conv weight gradients go straight into direct_grads' cat:
+            # their folds can wait for one grouped launch (DRL_WRW_DEFER)
+            self.mp.direct_grads(loss, getattr(self, "_direct_list", None),
+                                 defer_wrw=True)
         else:
             self.optim.zero_grad(set_to_none=False)
             loss.backward()

@@ -8,6 +8,7 @@ eager PyTorch. Set DRL_ALLOW_EAGER=1 to override (debug only).
 
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
@@ -98,6 +99,74 @@ def conv_supported(H, W, C, KH, KW, S, COUT, u8: bool, chw_out: bool = False,
         ext.conv_fwd_supported(H, W, C, KH, KW, S, COUT, u8, chw_out, njobs))
 
 
+def _gate(name: str, default: bool) -> bool:
+    """Read at call time: '1' forces the own kernel, '0' the library; unset
+    takes the measured default."""
+    v = os.environ.get(name)
+    if v is None or v == "":
+        return default
+    return v == "1"
+
+
+# default of DRL_WRW_DEFER (one grouped fold at the end of a direct_grads
+# backward instead of one fold behind every layer's wrw), decided by the A/B
+# in profiles/r09_apex_wrw.md
+_WRW_DEFER_DEFAULT = True
+
+_MAX_FOLD_JOBS = 4  # kMaxFoldJobs of conv_mfma.hip
+
+# (part, mb, b_part, gw, gb) of the wrw launches whose fold is still owed;
+# None outside deferred_wrw_folds(). A module global, not a thread-local:
+# autograd runs the backward nodes on its own device thread. So one backward
+# at a time per process while a context is open: a fused-conv backward that
+# another Python thread runs meanwhile would join the open context's list.
+_pending_wrw_folds = None
+
+
+def _launch_pending_folds(pending) -> None:
+    ext = hip_ext()
+    empty = None
+    for i in range(0, len(pending), _MAX_FOLD_JOBS):
+        jobs = pending[i : i + _MAX_FOLD_JOBS]
+        if empty is None:
+            empty = torch.empty(0, device=jobs[0][3].device)
+        ext.wrw_fold_grouped(
+            [j[0] for j in jobs], [j[1] for j in jobs],
+            [j[2] for j in jobs], [j[3] for j in jobs],
+            [j[4] if j[4] is not None else empty for j in jobs])
+    pending.clear()
+
+
+@contextlib.contextmanager
+def deferred_wrw_folds():
+    """Inside, the fused convs' weight-gradient backward launches only its
+    wrw kernel and returns gw / gb UNFILLED; on normal exit one grouped fold
+    per up to four layers fills them (same stream, so any later reader is
+    ordered behind it). For a caller that owns both the backward and the
+    first read of the gradients (MixedPrecisionTrainer.direct_grads): nothing
+    may read a conv weight gradient inside the context, and no other thread
+    may run a fused-conv backward while it is open (the list is process-wide,
+    see _pending_wrw_folds). An exception clears the list and launches
+    nothing. DRL_WRW_DEFER=0 (read on entry) makes the
+    context a no-op; a nested context joins the outer one."""
+    global _pending_wrw_folds
+    if (_pending_wrw_folds is not None
+            or not _gate("DRL_WRW_DEFER", _WRW_DEFER_DEFAULT)):
+        yield
+        return
+    pending = []
+    _pending_wrw_folds = pending
+    try:
+        yield
+    except BaseException:
+        pending.clear()
+        raise
+    finally:
+        _pending_wrw_folds = None
+    if pending:
+        _launch_pending_folds(pending)
+
+
 def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
                          need_x, need_w, need_b):
     """Backward of one fused conv+bias+ReLU layer (one job of
@@ -137,9 +206,14 @@ def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
                          device=x.device).permute(0, 3, 1, 2)
         gb = (torch.empty(COUT, dtype=torch.bfloat16, device=x.device)
               if need_b else None)
-        ext.conv_wrw(x, gout, gw,
-                     gb if need_b else torch.empty(0, device=x.device),
-                     stride)
+        if _pending_wrw_folds is not None:
+            part, mb, b_part = ext.conv_wrw_partials(x, gout, stride,
+                                                     bool(need_b))
+            _pending_wrw_folds.append((part, mb, b_part, gw, gb))
+        else:
+            ext.conv_wrw(x, gout, gw,
+                         gb if need_b else torch.empty(0, device=x.device),
+                         stride)
     elif use_own_wrw:
         # DRL_WRW_BF16=0: fp32 workspaces + cast launches (the A/B
         # baseline of the direct bf16 store)
@@ -298,15 +372,6 @@ def fused_conv_relu(x, weight, bias, stride: int, chw_out: bool = False):
 def conv3x3_supported(H, W, C, COUT) -> bool:
     ext = hip_ext(required=False)
     return ext is not None and bool(ext.conv3x3p1_supported(H, W, C, COUT))
-
-
-def _gate(name: str, default: bool) -> bool:
-    """Read at call time: '1' forces the own kernel, '0' the library; unset
-    takes the measured default."""
-    v = os.environ.get(name)
-    if v is None or v == "":
-        return default
-    return v == "1"
 
 
 # defaults of DRL_OWN_RESCONV_WRW / DRL_OWN_RESCONV_DGRAD, decided by the A/B

@@ -24,6 +24,7 @@
 
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <tuple>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -402,18 +403,18 @@ __global__ __launch_bounds__(256) void conv_wrw_kernel(
 // fp32 sums (round-to-nearest-even, what Tensor.to(bfloat16) does) and
 // writes the bf16 gradients directly — (COUT, K) in (kh, kw, c) order IS the
 // channels_last weight layout, so no cast or relayout pass follows.
+// block: 0 .. e_blocks (the last one only with bias); sh4_raw: 256 float4.
 template <typename OutT>
-__global__ __launch_bounds__(256) void wrw_reduce_kernel(
+__device__ __forceinline__ void wrw_reduce_block(
     const float* __restrict__ part, int planes, int n_elem,
     OutT* __restrict__ out, const float* __restrict__ b_part, int b_planes,
-    int cout, OutT* __restrict__ b_out) {
-  __shared__ __attribute__((aligned(16))) float sh4_raw[256 * 4];
+    int cout, OutT* __restrict__ b_out, int block, float* sh4_raw) {
   float* sh = sh4_raw;
   const int tid = threadIdx.x;
   const int e_blocks = (n_elem + 63) / 64;
-  if ((int)blockIdx.x < e_blocks) {
+  if (block < e_blocks) {
     // 16 lanes x float4 = 64 elements; 16 plane groups (n_elem % 64 == 0)
-    const int e4 = blockIdx.x * 64 + (tid & 15) * 4;
+    const int e4 = block * 64 + (tid & 15) * 4;
     const int g = tid >> 4;
     float4 s = {0.0f, 0.0f, 0.0f, 0.0f};
     // four loads in flight per lane (the pass is latency-bound otherwise);
@@ -465,6 +466,50 @@ __global__ __launch_bounds__(256) void wrw_reduce_kernel(
   }
 }
 
+template <typename OutT>
+__global__ __launch_bounds__(256) void wrw_reduce_kernel(
+    const float* __restrict__ part, int planes, int n_elem,
+    OutT* __restrict__ out, const float* __restrict__ b_part, int b_planes,
+    int cout, OutT* __restrict__ b_out) {
+  __shared__ __attribute__((aligned(16))) float sh4_raw[256 * 4];
+  wrw_reduce_block<OutT>(part, planes, n_elem, out, b_part, b_planes, cout,
+                         b_out, (int)blockIdx.x, sh4_raw);
+}
+
+// The same fold for up to kMaxFoldJobs weight gradients in one launch: the
+// job table travels by value (like ConvJobs), job j owns the next
+// e_blocks(j) + (bias ? 1 : 0) blocks, and each block runs wrw_reduce_block
+// unchanged, so a job's result has the bits of its own wrw_reduce_kernel
+// launch. The folds of a backward are latency-bound gathers of 128-576
+// blocks each; one launch at the end of the backward replaces one launch
+// behind every layer's wrw.
+constexpr int kMaxFoldJobs = 4;
+template <typename OutT>
+struct WrwFoldJobs {
+  const float* part[kMaxFoldJobs];
+  OutT* out[kMaxFoldJobs];
+  const float* b_part[kMaxFoldJobs];  // null: no bias block
+  OutT* b_out[kMaxFoldJobs];
+  int planes[kMaxFoldJobs], n_elem[kMaxFoldJobs];
+  int b_planes[kMaxFoldJobs], cout[kMaxFoldJobs];
+  int end_block[kMaxFoldJobs];  // prefix of e_blocks + bias over the jobs
+};
+
+template <typename OutT>
+__global__ __launch_bounds__(256) void wrw_reduce_grouped_kernel(
+    const WrwFoldJobs<OutT> jobs, int njobs) {
+  __shared__ __attribute__((aligned(16))) float sh4_raw[256 * 4];
+  const int b = blockIdx.x;
+  int job = 0;
+#pragma unroll
+  for (int j = 0; j < kMaxFoldJobs - 1; ++j)
+    if (j + 1 < njobs && b >= jobs.end_block[j]) job = j + 1;
+  const int first = job == 0 ? 0 : jobs.end_block[job - 1];
+  wrw_reduce_block<OutT>(jobs.part[job], jobs.planes[job], jobs.n_elem[job],
+                         jobs.out[job], jobs.b_part[job], jobs.b_planes[job],
+                         jobs.cout[job], jobs.b_out[job], b - first, sh4_raw);
+}
+
 // bias grad: column sum of the (M, COUT) relu-masked gout — torch's
 // strided bf16 reduce on channels_last costs ~11 us; this is one pass with
 // an ordered block-level LDS reduction; each block writes its COUT partial
@@ -502,6 +547,9 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(
     out[(int64_t)blockIdx.x * COUT + tid] = s;  // per-block partial
   }
 }
+
+// blocks of a colsum_bf16_kernel launch = rows of its b_part
+constexpr int kColsumBlocks = 256;
 
 }  // namespace
 
@@ -2021,6 +2069,10 @@ int wrw_resident_blocks(const StemLaunch& L) {
                          L.wrw_lds_bytes, "conv3x3c4_wrw");
 }
 
+void launch_wrw_reduce(const torch::Tensor& part, int mb,
+                       const torch::Tensor& b_part, int64_t COUT,
+                       torch::Tensor& gw_ws, torch::Tensor& gb_ws, bool bias);
+
 // Ordered fold shared by every weight-grad: wrw_reduce_kernel sums the mb
 // partial planes of `part` into gw_ws (fp32 workspace, or bf16 = the
 // gradient itself); with bias, colsum's per-block column sums of gout
@@ -2029,17 +2081,24 @@ void launch_wrw_fold(const torch::Tensor& part, int mb,
                      const torch::Tensor& gout, int M, int64_t COUT,
                      void (*colsum)(const __bf16*, int64_t, float*),
                      torch::Tensor& gw_ws, torch::Tensor& gb_ws, bool bias) {
-  constexpr int kColsumBlocks = 256;
-  auto st = cur_stream();
-  const int n_elem = (int)gw_ws.numel();
-  const bool bf16_out = gw_ws.scalar_type() == kBF16;
   torch::Tensor b_part;
   if (bias) {
     b_part = torch::empty({(int64_t)kColsumBlocks, COUT}, part.options());
-    hipLaunchKernelGGL(colsum, dim3(kColsumBlocks), dim3(256), 0, st,
-                       (const __bf16*)gout.data_ptr(), (int64_t)M,
-                       b_part.data_ptr<float>());
+    hipLaunchKernelGGL(colsum, dim3(kColsumBlocks), dim3(256), 0,
+                       cur_stream(), (const __bf16*)gout.data_ptr(),
+                       (int64_t)M, b_part.data_ptr<float>());
   }
+  launch_wrw_reduce(part, mb, b_part, COUT, gw_ws, gb_ws, bias);
+}
+
+// wrw_reduce_kernel on its own: b_part holds kColsumBlocks x COUT column-sum
+// partials when bias is set
+void launch_wrw_reduce(const torch::Tensor& part, int mb,
+                       const torch::Tensor& b_part, int64_t COUT,
+                       torch::Tensor& gw_ws, torch::Tensor& gb_ws, bool bias) {
+  auto st = cur_stream();
+  const int n_elem = (int)gw_ws.numel();
+  const bool bf16_out = gw_ws.scalar_type() == kBF16;
   const int e_blocks = (n_elem + 63) / 64;
   const float* b_part_ptr =
       bias ? (const float*)b_part.data_ptr<float>() : nullptr;
@@ -2187,13 +2246,17 @@ bool conv_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
   return e && e->wrw;
 }
 
-// in: (N,C,H,W) channels_last u8/bf16; gout: (N,COUT,P,Q) channels_last bf16
-// (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 and gb_ws: (COUT) fp32
-// (or empty), both fully overwritten. bf16 gw_ws/gb_ws are the gradients
-// themselves: gw_ws then holds COUT*KH*KW*C elements in (cout, kh, kw, c)
-// memory order (a channels_last weight-shaped tensor or its flat view).
-void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
-              torch::Tensor gb_ws, int64_t stride) {
+namespace {
+
+// a checked wrw call: table entry and row count
+struct WrwCall {
+  const ConvEntry* L;
+  int64_t N, COUT;
+  int M;
+};
+
+WrwCall check_wrw_inputs(const torch::Tensor& in, const torch::Tensor& gout,
+                         int64_t stride) {
   TORCH_CHECK(in.dim() == 4 && gout.dim() == 4 && stride >= 1,
               "conv_wrw wants 4-D in and gout and a positive stride");
   const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
@@ -2207,34 +2270,216 @@ void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
   TORCH_CHECK(L && L->wrw, "no wrw kernel for this geometry");
   check_nhwc(in, u8 ? torch::kUInt8 : kBF16, N, C, H, W, "conv_wrw in");
   check_nhwc(gout, kBF16, N, COUT, P, Q, "conv_wrw gout (in's batch)");
-  const bool bf16_out = gw_ws.scalar_type() == kBF16;
-  check_dev(gw_ws, bf16_out ? kBF16 : torch::kFloat32, "conv_wrw gw_ws");
-  TORCH_CHECK(gw_ws.is_contiguous() ||
-              (gw_ws.dim() == 4 &&
-               gw_ws.is_contiguous(at::MemoryFormat::ChannelsLast)));
-  const int n_elem = (int)gw_ws.numel();
-  TORCH_CHECK(gw_ws.numel() == COUT * L->g.K(), "gw_ws shape mismatch");
-  const bool bias = gb_ws.defined() && gb_ws.numel() > 0;
-  if (bias) check_rows(gb_ws, gw_ws.scalar_type(), {COUT}, "conv_wrw gb_ws");
-  const int M = checked_rows(N * P * Q, "conv_wrw");
+  // 16-byte pieces of both
+  TORCH_CHECK((uintptr_t)in.data_ptr() % 16 == 0 &&
+                  (uintptr_t)gout.data_ptr() % 16 == 0,
+              "conv_wrw: misaligned tensor");
+  return WrwCall{L, N, COUT, checked_rows(N * P * Q, "conv_wrw")};
+}
+
+// What wrw_reduce_block dereferences for one job, checked: part (planes,
+// n_elem + kPlanePad) fp32; gw n_elem elements of `dtype`, dense in (cout,
+// kh, kw, c) order; b_part (b_planes, cout) fp32 and gb (cout) of gw's
+// dtype, or both empty.
+struct FoldJob {
+  int planes, n_elem, b_planes, cout;
+  bool bias;
+};
+
+// the output half of check_fold_job: planes and b_planes stay 0
+FoldJob check_fold_out(const torch::Tensor& gw, const torch::Tensor& gb,
+                       at::ScalarType dtype) {
+  TORCH_CHECK(gw.defined(), "wrw fold gw is undefined");
+  TORCH_CHECK(dtype == kBF16 || dtype == torch::kFloat32,
+              "wrw fold writes fp32 or bf16");
+  check_dev(gw, dtype, "wrw fold gw");
+  TORCH_CHECK(gw.is_contiguous() ||
+                  (gw.dim() == 4 &&
+                   gw.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              "wrw fold gw must be dense in (cout, kh, kw, c) order");
+  const int64_t n_elem = gw.numel();
+  TORCH_CHECK(n_elem > 0 && n_elem % 64 == 0 && n_elem < ((int64_t)1 << 30),
+              "wrw fold gw must hold a positive multiple of 64 elements");
+  TORCH_CHECK((uintptr_t)gw.data_ptr() % 16 == 0, "wrw fold gw is misaligned");
+  FoldJob j{0, (int)n_elem, 0, 0, gb.defined() && gb.numel() > 0};
+  if (j.bias) {
+    const int64_t cout = gb.numel();
+    TORCH_CHECK(cout <= 256 && 256 % cout == 0,
+                "wrw fold bias: cout must divide 256");
+    check_rows(gb, dtype, {cout}, "wrw fold gb");
+    TORCH_CHECK(gb.device() == gw.device(), "wrw fold: tensors on two devices");
+    j.cout = (int)cout;
+  }
+  return j;
+}
+
+FoldJob check_fold_job(const torch::Tensor& part, int64_t mb,
+                       const torch::Tensor& b_part, const torch::Tensor& gw,
+                       const torch::Tensor& gb, at::ScalarType dtype) {
+  FoldJob j = check_fold_out(gw, gb, dtype);
+  const int64_t n_elem = j.n_elem;
+  TORCH_CHECK(mb >= 1 && mb < ((int64_t)1 << 20), "wrw fold wants >= 1 plane");
+  check_rows(part, torch::kFloat32, {mb, n_elem + kPlanePad},
+             "wrw fold partial planes");
+  TORCH_CHECK((uintptr_t)part.data_ptr() % 16 == 0,
+              "wrw fold partial planes are misaligned");
+  TORCH_CHECK(part.device() == gw.device(), "wrw fold: tensors on two devices");
+  j.planes = (int)mb;
+  const bool has_b_part = b_part.defined() && b_part.numel() > 0;
+  TORCH_CHECK(j.bias == has_b_part,
+              "wrw fold wants b_part and gb together or neither");
+  if (j.bias) {
+    const int64_t cout = j.cout;
+    TORCH_CHECK(b_part.dim() == 2 && b_part.size(0) >= 1 &&
+                    b_part.size(0) < ((int64_t)1 << 20),
+                "wrw fold b_part must be (b_planes, cout)");
+    check_rows(b_part, torch::kFloat32, {b_part.size(0), cout},
+               "wrw fold b_part");
+    TORCH_CHECK(b_part.device() == gw.device(),
+                "wrw fold: tensors on two devices");
+    j.b_planes = (int)b_part.size(0);
+  }
+  return j;
+}
+
+// m-slices of a call: scale the m-grid with the batch — R2D2/IMPALA run
+// 8-20x Ape-X's row count through the same kernel (conv1 wrw measured 139 us
+// at 1.02M rows with 512 blocks = 250 serial chunks per block); every
+// m-slice costs one partial plane of write + read traffic
+int wrw_mblocks(const ConvEntry& L, int M) {
   const int n_chunks = (M + 31) / 32;
-  // scale the m-grid with the batch: R2D2/IMPALA run 8-20x Ape-X's row
-  // count through the same kernel (conv1 wrw measured 139 us at 1.02M
-  // rows with 512 blocks = 250 serial chunks per block)
-  int mb = (n_chunks > 8192 ? 2048 : 512) / L->ktiles;  // every m-slice costs one partial plane of write + read traffic
+  int mb = (n_chunks > 8192 ? 2048 : 512) / L.ktiles;
   if (mb > n_chunks) mb = n_chunks;
   if (mb < 1) mb = 1;
-  auto st = cur_stream();
-  // per-m-slice partial planes (every (ktile, m-slice) block writes its
-  // whole 64 x COUT tile, so no zero-fill) + ordered reduction
-  const auto f32 = gw_ws.options().dtype(torch::kFloat32);
-  auto part = torch::empty({(int64_t)mb, (int64_t)n_elem + kPlanePad}, f32);
-  hipLaunchKernelGGL(L->wrw, dim3(L->ktiles, mb), dim3(256), L->wrw_lds_bytes,
-                     st, (const void*)in.data_ptr(),
-                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
-                     (int)N, mb);
-  launch_wrw_fold(part, mb, gout, M, COUT, L->colsum, gw_ws, gb_ws, bias);
+  return mb;
 }
+
+// The wrw launches of a checked call: per-m-slice partial planes (every
+// (ktile, m-slice) block writes its whole 64 x COUT tile, so no zero-fill)
+// and, with want_bias, colsum_bf16_kernel's kColsumBlocks x COUT column-sum
+// partials of gout.
+struct WrwPartials {
+  torch::Tensor part, b_part;
+  int mb;
+};
+
+WrwPartials launch_wrw_partials(const WrwCall& c, const torch::Tensor& in,
+                                const torch::Tensor& gout, bool want_bias) {
+  const ConvEntry& L = *c.L;
+  const int mb = wrw_mblocks(L, c.M);
+  const int64_t n_elem = c.COUT * L.g.K();
+  const auto f32 = gout.options().dtype(torch::kFloat32);
+  WrwPartials r;
+  r.mb = mb;
+  r.part = torch::empty({(int64_t)mb, n_elem + kPlanePad}, f32);
+  auto st = cur_stream();
+  hipLaunchKernelGGL(L.wrw, dim3(L.ktiles, mb), dim3(256), L.wrw_lds_bytes, st,
+                     (const void*)in.data_ptr(),
+                     (const __bf16*)gout.data_ptr(), r.part.data_ptr<float>(),
+                     (int)c.N, mb);
+  if (want_bias) {
+    r.b_part = torch::empty({(int64_t)kColsumBlocks, c.COUT}, f32);
+    hipLaunchKernelGGL(L.colsum, dim3(kColsumBlocks), dim3(256), 0, st,
+                       (const __bf16*)gout.data_ptr(), (int64_t)c.M,
+                       r.b_part.data_ptr<float>());
+  }
+  return r;
+}
+
+// wrw_reduce_grouped_kernel over checked jobs
+template <typename OutT>
+void launch_fold_grouped(const std::vector<FoldJob>& jobs,
+                         const std::vector<torch::Tensor>& parts,
+                         const std::vector<torch::Tensor>& b_parts,
+                         const std::vector<torch::Tensor>& gws,
+                         const std::vector<torch::Tensor>& gbs) {
+  WrwFoldJobs<OutT> t{};
+  int blocks = 0;
+  for (size_t j = 0; j < jobs.size(); ++j) {
+    t.part[j] = parts[j].data_ptr<float>();
+    t.out[j] = (OutT*)gws[j].data_ptr();
+    t.b_part[j] = jobs[j].bias ? b_parts[j].data_ptr<float>() : nullptr;
+    t.b_out[j] = jobs[j].bias ? (OutT*)gbs[j].data_ptr() : nullptr;
+    t.planes[j] = jobs[j].planes;
+    t.n_elem[j] = jobs[j].n_elem;
+    t.b_planes[j] = jobs[j].b_planes;
+    t.cout[j] = jobs[j].cout;
+    blocks += jobs[j].n_elem / 64 + (jobs[j].bias ? 1 : 0);
+    t.end_block[j] = blocks;
+  }
+  hipLaunchKernelGGL(wrw_reduce_grouped_kernel<OutT>, dim3(blocks), dim3(256),
+                     0, cur_stream(), t, (int)jobs.size());
+}
+
+}  // namespace
+
+// in: (N,C,H,W) channels_last u8/bf16; gout: (N,COUT,P,Q) channels_last bf16
+// (already relu-masked); gw_ws: (COUT, KH*KW*C) fp32 and gb_ws: (COUT) fp32
+// (or empty), both fully overwritten. bf16 gw_ws/gb_ws are the gradients
+// themselves: gw_ws then holds COUT*KH*KW*C elements in (cout, kh, kw, c)
+// memory order (a channels_last weight-shaped tensor or its flat view).
+// = conv_wrw_partials + a one-job wrw_fold_grouped.
+void conv_wrw(torch::Tensor in, torch::Tensor gout, torch::Tensor gw_ws,
+              torch::Tensor gb_ws, int64_t stride) {
+  const WrwCall c = check_wrw_inputs(in, gout, stride);
+  // the fold's outputs, before the first launch
+  TORCH_CHECK(gw_ws.defined(), "conv_wrw gw_ws is undefined");
+  const bool bias = check_fold_out(gw_ws, gb_ws, gw_ws.scalar_type()).bias;
+  TORCH_CHECK(gw_ws.numel() == c.COUT * c.L->g.K(), "gw_ws shape mismatch");
+  if (bias)
+    check_rows(gb_ws, gw_ws.scalar_type(), {c.COUT}, "conv_wrw gb_ws");
+  TORCH_CHECK(gw_ws.device() == gout.device(), "conv_wrw: two devices");
+  WrwPartials r = launch_wrw_partials(c, in, gout, bias);
+  const FoldJob job = check_fold_job(r.part, r.mb, r.b_part, gw_ws, gb_ws,
+                                     gw_ws.scalar_type());
+  if (gw_ws.scalar_type() == kBF16)
+    launch_fold_grouped<__bf16>({job}, {r.part}, {r.b_part}, {gw_ws}, {gb_ws});
+  else
+    launch_fold_grouped<float>({job}, {r.part}, {r.b_part}, {gw_ws}, {gb_ws});
+}
+
+// The wrw launches alone: (part, mb, b_part) for wrw_fold_grouped; b_part is
+// an empty tensor without want_bias.
+std::tuple<torch::Tensor, int64_t, torch::Tensor> conv_wrw_partials(
+    torch::Tensor in, torch::Tensor gout, int64_t stride, bool want_bias) {
+  const WrwCall c = check_wrw_inputs(in, gout, stride);
+  WrwPartials r = launch_wrw_partials(c, in, gout, want_bias);
+  if (!want_bias) r.b_part = torch::empty({0}, r.part.options());
+  return {r.part, (int64_t)r.mb, r.b_part};
+}
+
+// Ordered fold of 1..kMaxFoldJobs weight gradients in one launch. Job j:
+// parts[j] (mbs[j], n_elem + plane pad) fp32 planes -> gws[j] (n_elem
+// elements, fp32 or bf16, one dtype for all jobs); b_parts[j] (b_planes,
+// cout) fp32 -> gbs[j] (cout) of the same dtype, or both empty for a job
+// without bias. Every job is checked before the launch.
+void wrw_fold_grouped(std::vector<torch::Tensor> parts,
+                      std::vector<int64_t> mbs,
+                      std::vector<torch::Tensor> b_parts,
+                      std::vector<torch::Tensor> gws,
+                      std::vector<torch::Tensor> gbs) {
+  const size_t n = parts.size();
+  TORCH_CHECK(n >= 1 && n <= (size_t)kMaxFoldJobs, "1..", kMaxFoldJobs,
+              " fold jobs per launch");
+  TORCH_CHECK(mbs.size() == n && b_parts.size() == n && gws.size() == n &&
+                  gbs.size() == n,
+              "wrw_fold_grouped wants one entry per job in every list");
+  TORCH_CHECK(gws[0].defined(), "wrw fold gw is undefined");
+  const at::ScalarType dtype = gws[0].scalar_type();
+  std::vector<FoldJob> jobs;
+  for (size_t j = 0; j < n; ++j) {
+    jobs.push_back(
+        check_fold_job(parts[j], mbs[j], b_parts[j], gws[j], gbs[j], dtype));
+    TORCH_CHECK(gws[j].device() == gws[0].device(),
+                "wrw fold: jobs on two devices");
+  }
+  if (dtype == kBF16)
+    launch_fold_grouped<__bf16>(jobs, parts, b_parts, gws, gbs);
+  else
+    launch_fold_grouped<float>(jobs, parts, b_parts, gws, gbs);
+}
+
+int64_t wrw_plane_pad() { return kPlanePad; }
 
 bool conv_dgrad_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
                           int64_t KW, int64_t S, int64_t COUT) {
@@ -2619,6 +2864,11 @@ void register_conv(pybind11::module_& m) {
   m.def("conv_wrw", &conv_wrw,
         "MFMA conv weight-grad; gw/gb are fp32 workspaces or bf16 grads");
   m.def("conv_wrw_supported", &conv_wrw_supported);
+  m.def("conv_wrw_partials", &conv_wrw_partials,
+        "wrw launch only -> (part, mb, b_part) for wrw_fold_grouped");
+  m.def("wrw_fold_grouped", &wrw_fold_grouped,
+        "ordered fold of up to 4 weight gradients in one launch");
+  m.def("wrw_plane_pad", &wrw_plane_pad);
   m.def("conv_dgrad", &conv_dgrad,
         "MFMA conv data-grad (masked-tap gather, pre-transposed weights)");
   m.def("conv_dgrad_supported", &conv_dgrad_supported);

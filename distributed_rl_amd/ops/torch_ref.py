@@ -469,3 +469,46 @@ def fold_nstep_reward(rewards: torch.Tensor, gamma: float) -> torch.Tensor:
     n = rewards.shape[-1]
     disc = gamma ** torch.arange(n, dtype=rewards.dtype, device=rewards.device)
     return (rewards * disc).sum(-1)
+
+
+# ---------------------------------------------------------------------------
+# ordered fold of the weight-gradient partial planes (conv_mfma.hip,
+# wrw_reduce_block) — the same fp32 additions in the same order
+# ---------------------------------------------------------------------------
+
+
+def wrw_fold_ordered(part: torch.Tensor, n_elem: int, b_part=None,
+                     out_dtype: torch.dtype = torch.float32):
+    """part: (planes, >= n_elem) fp32, columns past n_elem are padding.
+    Element e: 16 plane groups, group g adds planes g, g+16, g+32, ... in
+    that order onto 0, then t = ((s_0 + s_1) + ...) + s_15. b_part: optional
+    (b_planes, cout) fp32 with cout dividing 256; column c: G = 256 // cout
+    groups, group g adds rows g, g+G, ... onto 0, then the group sums are
+    added onto 0 in group order. Returns (gw, gb or None), rounded to
+    out_dtype (round-to-nearest-even) at the very end."""
+    p = part.detach().to("cpu", torch.float32)[:, :n_elem]
+    planes = p.shape[0]
+    sums = []
+    for g in range(16):
+        s = torch.zeros(n_elem, dtype=torch.float32)
+        for k in range(g, planes, 16):
+            s = s + p[k]
+        sums.append(s)
+    t = sums[0]
+    for g in range(1, 16):
+        t = t + sums[g]
+    gw = t.to(out_dtype)
+    gb = None
+    if b_part is not None:
+        b = b_part.detach().to("cpu", torch.float32)
+        b_planes, cout = b.shape
+        assert 256 % cout == 0
+        G = 256 // cout
+        tb = torch.zeros(cout, dtype=torch.float32)
+        for g in range(G):
+            s = torch.zeros(cout, dtype=torch.float32)
+            for k in range(g, b_planes, G):
+                s = s + b[k]
+            tb = tb + s
+        gb = tb.to(out_dtype)
+    return gw, gb

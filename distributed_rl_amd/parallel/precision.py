@@ -19,6 +19,7 @@ Every step op is a fixed-shape kernel -> hipGraph-capturable.
 
 from __future__ import annotations
 
+import contextlib
 import copy
 from typing import Callable, Optional
 
@@ -163,7 +164,7 @@ class MixedPrecisionTrainer:
         for g in self.groups:
             g.flat_cgrad.zero_()
 
-    def direct_grads(self, loss, params_override=None):
+    def direct_grads(self, loss, params_override=None, defer_wrw=False):
         """Backward WITHOUT AccumulateGrad: torch.autograd.grad returns each
         parameter's gradient as the tensor its producing op wrote (no
         ``.grad += new`` add kernel per parameter — ~12 x 4.9 us per Ape-X
@@ -175,10 +176,21 @@ class MixedPrecisionTrainer:
         params_override: the actual autograd leaves when the forward used
         fused views (e.g. Ape-X's w1 spanning the two pinned dueling-stream
         weights) — their flattened concatenation must equal the flat-buffer
-        layout (single-group trainers only)."""
+        layout (single-group trainers only).
+
+        defer_wrw: run the backward inside ops.deferred_wrw_folds() — the
+        fused convs' weight gradients come back unfilled and one grouped
+        fold fills them before the cat below, the first reader. Only for a
+        graph in which nothing else reads a conv weight gradient."""
+        if defer_wrw:
+            from ..ops import deferred_wrw_folds
+            backward_ctx = deferred_wrw_folds
+        else:
+            backward_ctx = contextlib.nullcontext
         if params_override is not None:
             assert len(self.groups) == 1
-            grads = torch.autograd.grad(loss, params_override)
+            with backward_ctx():
+                grads = torch.autograd.grad(loss, params_override)
             flats = []
             for p, gr in zip(params_override, grads):
                 if gr.dim() == 4 and _is_cl(p) and not _is_cl(gr):
@@ -187,7 +199,8 @@ class MixedPrecisionTrainer:
             torch.cat(flats, out=self.groups[0].flat_cgrad)
             return
         params = [cp for g in self.groups for cp in g.c_params]
-        grads = torch.autograd.grad(loss, params)
+        with backward_ctx():
+            grads = torch.autograd.grad(loss, params)
         i = 0
         for g in self.groups:
             n = len(g.c_params)
