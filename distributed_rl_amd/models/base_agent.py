@@ -319,8 +319,9 @@ _RESCONV_DEFAULT = True
 
 
 def _resconv_ok(x: torch.Tensor, *convs: nn.Conv2d) -> bool:
-    """Fused 3x3 pad-1 path (ops/hip/conv_mfma.hip conv3x3p1_fwd_kernel):
-    CUDA bf16 channels_last input, bf16 weights, every conv's geometry
+    """Fused 3x3 pad-1 path (ops/hip/conv_mfma.hip conv3x3p1_fwd_kernel at
+    a table geometry, conv3x3p1_fwd_hw_kernel at any other frame size):
+    CUDA bf16 channels_last input, bf16 weights, every conv's (C, COUT)
     covered, gate on."""
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
         return False
@@ -351,9 +352,10 @@ def _resconv_ok(x: torch.Tensor, *convs: nn.Conv2d) -> bool:
 def _stem_ok(x: torch.Tensor, conv: nn.Conv2d) -> bool:
     """Own stem-conv path (ops/hip/conv_mfma.hip conv3x3c4_*_kernel): the
     3x3 stride-1 pad-1 conv on CUDA bf16 channels_last input, bf16
-    channels_last weight, at the one geometry the kernel has (84x84,
-    C=4 -> 16); gate DRL_OWN_STEM ('1' own kernel, '0' or unset library:
-    ops._STEM_DEFAULT, profiles/r08_stem_conv.md)."""
+    channels_last weight, C=4 -> 16 at any frame size (84x84 on the table
+    kernel, every other size on the run-time H, W kernel); gate
+    DRL_OWN_STEM ('1' own kernel, '0' or unset library: ops._STEM_DEFAULT,
+    profiles/r08_stem_conv.md)."""
     w = conv.weight
     if tuple(w.shape[2:]) != (3, 3) or conv.stride != (1, 1) \
             or conv.padding != (1, 1) or conv.dilation != (1, 1) \
@@ -429,9 +431,11 @@ class ImpalaResNet(nn.Module):
     ResNet V-trace, 8x MI355X learner-DP'). Beyond the reference repo's
     capability (it only ships the shallow torso) — netCat: IMPALA_RESNET.
 
-    On bf16 channels_last GPU input the 3x3 pad-1 convs whose geometry the
-    hand-written kernel covers (everything but the first, C=4 conv at
-    84x84) run through ops.fused_conv3x3 when DRL_OWN_RESCONV allows, and
+    On bf16 channels_last GPU input the 3x3 pad-1 convs whose channels the
+    hand-written kernels cover (16/32 -> 16/32: everything but the first,
+    C=4 conv) run through ops.fused_conv3x3 at any frame size when
+    DRL_OWN_RESCONV allows (the 84x84 sections on their table kernels,
+    other sizes on the run-time H, W kernels), and
     the 3x3 stride-2 pad-1 max-pools through ops.fused_maxpool3x3s2 (uint8
     tap plane, gather backward without atomics) when DRL_OWN_POOL allows.
     The first conv runs through ops.fused_stem_conv3x3 (own forward and

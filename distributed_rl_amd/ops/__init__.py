@@ -481,8 +481,8 @@ def fused_conv3x3(x, weight, bias, *, relu_in: bool = False,
                   relu_out: bool = False, residual=None):
     """3x3 stride-1 pad-1 conv with the residual-block fusions:
     ``relu?(conv(relu?(x)) + bias + residual?)``. Device tensors must be bf16
-    channels_last at a geometry conv3x3_supported() covers; CPU tensors take
-    the eager reference."""
+    channels_last at a geometry conv3x3_supported() covers (any frame size
+    at channels 16/32 -> 16/32); CPU tensors take the eager reference."""
     if _use_hip(x):
         return _FusedConv3x3Fn.apply(x, weight, bias, residual, bool(relu_in),
                                      bool(relu_out))
@@ -490,15 +490,20 @@ def fused_conv3x3(x, weight, bias, *, relu_in: bool = False,
 
 
 # ---------------------------------------------------------------------------
-# K2d — stem conv of the torso (3x3 pad-1, 84x84, C=4 -> 16): own forward
+# K2d — stem conv of the torso (3x3 pad-1, C=4 -> 16; 84x84 on the table
+# kernel, any other frame size on the run-time H, W kernel): own forward
 # and ordered weight gradient; the input gradient (never wanted in training:
 # the frames are data) stays on the library
 # ---------------------------------------------------------------------------
 
 
 def stem_conv_supported(H, W, C, COUT) -> bool:
+    """The table geometry (84x84), or any H, W >= 1 at a (C, COUT) the
+    run-time H, W stem kernel has."""
     ext = hip_ext(required=False)
-    return ext is not None and bool(ext.conv3x3c4_supported(H, W, C, COUT))
+    return ext is not None and H >= 1 and W >= 1 and bool(
+        ext.conv3x3c4_supported(H, W, C, COUT)
+        or ext.conv3x3c4_hw_supported(C, COUT))
 
 
 # default of DRL_OWN_STEM (read by models/base_agent.py). Off: the existing
@@ -511,8 +516,10 @@ _STEM_DEFAULT = False
 
 
 class _FusedStemConvFn(torch.autograd.Function):
-    """Forward on conv3x3c4_fwd_kernel. Backward: the own weight and bias
-    gradient (conv3x3c4_wrw, ordered planes, gate DRL_OWN_STEM_WRW);
+    """Forward on conv3x3c4_fwd_kernel at the table geometry and on
+    conv3x3c4_fwd_hw_kernel (run-time H, W) at any other frame size.
+    Backward: the own weight and bias gradient (conv3x3c4_wrw or
+    conv3x3c4_wrw_hw, ordered planes, gate DRL_OWN_STEM_WRW);
     aten.convolution_backward runs only what that leaves over — the input
     gradient when x requires one, and everything when the gate is closed."""
 
@@ -525,7 +532,10 @@ class _FusedStemConvFn(torch.autograd.Function):
             N, COUT, H, W, dtype=torch.bfloat16, device=x.device,
             memory_format=torch.channels_last,
         )
-        ext.conv3x3c4_fwd(
+        C = x.shape[1]
+        fwd = (ext.conv3x3c4_fwd if ext.conv3x3c4_supported(H, W, C, COUT)
+               else ext.conv3x3c4_fwd_hw)
+        fwd(
             x, weight,
             bias if bias is not None
             else torch.empty(0, device=x.device, dtype=torch.bfloat16), out)
@@ -544,8 +554,9 @@ class _FusedStemConvFn(torch.autograd.Function):
         need_w = ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         C, H, W = x.shape[1], x.shape[2], x.shape[3]
+        table = bool(ext.conv3x3c4_wrw_supported(H, W, C, COUT))
         own_wrw = need_w and _gate("DRL_OWN_STEM_WRW", True) \
-            and bool(ext.conv3x3c4_wrw_supported(H, W, C, COUT))
+            and (table or bool(ext.conv3x3c4_hw_supported(C, COUT)))
         gx = gw = gb = None
         if own_wrw:
             # (COUT, 36) in (kh, kw, c) order is the channels_last layout
@@ -553,8 +564,9 @@ class _FusedStemConvFn(torch.autograd.Function):
                              device=x.device).permute(0, 3, 1, 2)
             gb = (torch.empty(COUT, dtype=torch.bfloat16, device=x.device)
                   if need_b else None)
-            ext.conv3x3c4_wrw(x, gout, gw,
-                              gb if need_b else torch.empty(0, device=x.device))
+            wrw = ext.conv3x3c4_wrw if table else ext.conv3x3c4_wrw_hw
+            wrw(x, gout, gw,
+                gb if need_b else torch.empty(0, device=x.device))
         lib = [need_x, need_w and not own_wrw, need_b and not own_wrw]
         if any(lib):
             gx2, gw2, gb2 = torch.ops.aten.convolution_backward(

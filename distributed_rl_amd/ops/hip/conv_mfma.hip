@@ -872,8 +872,26 @@ struct Conv3Geom {
   static_assert(COUT <= 64, "bias staging uses the first COUT threads");
 };
 
-template <int H, int W, int C, int COUT, int WAVES, int RPW, bool MASK = false>
-__global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
+// The image extent of the four 3x3 pad-1 kernel bodies below (forward, wrw,
+// stem forward, stem wrw). H and W occur in a body only in the row decode,
+// the two bounds tests and the tap offset; tiling, LDS layout, fragment
+// maps and epilogues depend on (C, COUT) alone. Two implementations:
+//   * HwConst<H, W>: compile-time constants — the table kernels
+//     (kConv3Launches, kStemLaunches), whose code is what it was when H and
+//     W were template arguments of the body;
+//   * HwArgs: two ints passed as kernel arguments — the *_hw_kernel
+//     instantiations, one per (C, COUT), for every other frame size.
+template <int HC, int WC>
+struct HwConst {
+  static constexpr int H = HC, W = WC;
+};
+struct HwArgs {
+  int H, W;
+};
+
+template <class HW, int C, int COUT, int WAVES, int RPW, bool MASK>
+__device__ __forceinline__ void conv3x3p1_fwd_body(
+    const HW hw,
     const __bf16* __restrict__ in,        // (N,H,W,C) NHWC
     const __bf16* __restrict__ weight,    // (COUT, 9C) = (cout, kh, kw, c)
     const __bf16* __restrict__ bias,      // (COUT), may be null
@@ -882,6 +900,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
     __bf16* __restrict__ out,             // (N,H,W,COUT)
     int batch, int relu_in, int relu_out) {
   using G = Conv3Geom<C, COUT>;
+  const int H = hw.H, W = hw.W;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* wlds = reinterpret_cast<__bf16*>(smem);
 
@@ -1041,6 +1060,30 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
   }
 }
 
+// table kernel: H and W compile-time (kConv3Launches)
+template <int H, int W, int C, int COUT, int WAVES, int RPW, bool MASK = false>
+__global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_kernel(
+    const __bf16* __restrict__ in, const __bf16* __restrict__ weight,
+    const __bf16* __restrict__ bias, const __bf16* __restrict__ residual,
+    const __bf16* __restrict__ mask, __bf16* __restrict__ out, int batch,
+    int relu_in, int relu_out) {
+  conv3x3p1_fwd_body<HwConst<H, W>, C, COUT, WAVES, RPW, MASK>(
+      HwConst<H, W>{}, in, weight, bias, residual, mask, out, batch, relu_in,
+      relu_out);
+}
+
+// run-time kernel: H and W are arguments (kConv3HwLaunches)
+template <int C, int COUT, int WAVES, int RPW, bool MASK = false>
+__global__ __launch_bounds__(WAVES * 64) void conv3x3p1_fwd_hw_kernel(
+    const __bf16* __restrict__ in, const __bf16* __restrict__ weight,
+    const __bf16* __restrict__ bias, const __bf16* __restrict__ residual,
+    const __bf16* __restrict__ mask, __bf16* __restrict__ out, int batch,
+    int relu_in, int relu_out, int H, int W) {
+  conv3x3p1_fwd_body<HwArgs, C, COUT, WAVES, RPW, MASK>(
+      HwArgs{H, W}, in, weight, bias, residual, mask, out, batch, relu_in,
+      relu_out);
+}
+
 // ---------------------------------------------------------------------------
 // Weight gradient of the same convs:
 //   gw[co][(kh,kw,c)] = sum_m gout[m][co] * im2col(x)[m][(kh,kw,c)], M = N*H*W
@@ -1086,13 +1129,15 @@ struct Conv3Wrw {
   static_assert(XSTRIDE % 8 == 0 && GSTRIDE % 8 == 0, "16-byte LDS rows");
 };
 
-template <int H, int W, int C, int COUT, int R>
-__global__ __launch_bounds__(256) void conv3x3p1_wrw_kernel(
+template <class HW, int C, int COUT, int R>
+__device__ __forceinline__ void conv3x3p1_wrw_body(
+    const HW hw,
     const __bf16* __restrict__ x,     // (N,H,W,C) NHWC
     const __bf16* __restrict__ gout,  // (M, COUT) = NHWC grad (relu-masked)
     float* __restrict__ gw_part,      // (mblocks, COUT*K + kPlanePad) fp32
     int batch, int mblocks, int relu_in) {
   using G = Conv3Wrw<C, COUT, R>;
+  const int H = hw.H, W = hw.W;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* x_t = reinterpret_cast<__bf16*>(smem);  // [ROWS][XSTRIDE]
   __bf16* g_t = x_t + G::ROWS * G::XSTRIDE;       // [ROWS][GSTRIDE]
@@ -1222,6 +1267,24 @@ __global__ __launch_bounds__(256) void conv3x3p1_wrw_kernel(
   }
 }
 
+template <int H, int W, int C, int COUT, int R>
+__global__ __launch_bounds__(256) void conv3x3p1_wrw_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ gout,
+    float* __restrict__ gw_part, int batch, int mblocks, int relu_in) {
+  conv3x3p1_wrw_body<HwConst<H, W>, C, COUT, R>(HwConst<H, W>{}, x, gout,
+                                                gw_part, batch, mblocks,
+                                                relu_in);
+}
+
+template <int C, int COUT, int R>
+__global__ __launch_bounds__(256) void conv3x3p1_wrw_hw_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ gout,
+    float* __restrict__ gw_part, int batch, int mblocks, int relu_in, int H,
+    int W) {
+  conv3x3p1_wrw_body<HwArgs, C, COUT, R>(HwArgs{H, W}, x, gout, gw_part, batch,
+                                         mblocks, relu_in);
+}
+
 // Input gradient: for a 3x3 stride-1 pad-1 conv it is itself a 3x3 stride-1
 // pad-1 conv of gout with the weight transposed and flipped,
 //   W'[ci][kh][kw][co] = W[co][2-kh][2-kw][ci],
@@ -1299,6 +1362,61 @@ const Conv3Launch* find_conv3(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   return nullptr;
 }
 
+// The run-time entries: ONE per (C, COUT), Conv3Launch's fields with H and
+// W moved from the key to two trailing kernel arguments. A geometry that
+// kConv3Launches does not hold launches these.
+using Conv3HwFn = void (*)(const __bf16*, const __bf16*, const __bf16*,
+                           const __bf16*, const __bf16*, __bf16*, int, int,
+                           int, int, int);
+
+struct Conv3HwLaunch {
+  int C, COUT;
+  Conv3HwFn fn, fn_mask;
+  int lds_bytes;
+  int waves, rpw;
+  void (*wrw)(const __bf16*, const __bf16*, float*, int, int, int, int, int);
+  int wrw_lds_bytes, wrw_rows;
+  void (*colsum)(const __bf16*, int64_t, float*);
+};
+
+template <int C, int COUT, int WAVES, int RPW, int WRW_R>
+Conv3HwLaunch make_conv3_hw() {
+  using G = Conv3Geom<C, COUT>;
+  Conv3HwLaunch l{};
+  l.C = C; l.COUT = COUT;
+  l.fn = conv3x3p1_fwd_hw_kernel<C, COUT, WAVES, RPW, false>;
+  l.fn_mask = conv3x3p1_fwd_hw_kernel<C, COUT, WAVES, RPW, true>;
+  l.lds_bytes = G::LDS_BYTES;
+  l.waves = WAVES;
+  l.rpw = RPW;
+  if constexpr (WRW_R > 0) {
+    l.wrw = conv3x3p1_wrw_hw_kernel<C, COUT, WRW_R>;
+    l.wrw_lds_bytes = Conv3Wrw<C, COUT, WRW_R>::LDS_BYTES;
+    l.wrw_rows = 32 * WRW_R;
+    l.colsum = colsum_bf16_kernel<COUT>;
+  }
+  return l;
+}
+
+// tile shapes: kConv3Launches' values for the larger geometry of each
+// (C, COUT) pair; not swept at other frame sizes
+// (profiles/r10_resconv_any_hw.md)
+static const Conv3HwLaunch kConv3HwLaunches[] = {
+    make_conv3_hw<16, 16, 8, 32, 1>(),
+    make_conv3_hw<16, 32, 8, 32, 4>(),
+    make_conv3_hw<32, 32, 8, 32, 2>(),
+    // input gradient of a 16 -> 32 conv (forward kernels only)
+    make_conv3_hw<32, 16, 8, 32, 0>(),
+};
+
+const Conv3HwLaunch* find_conv3_hw(int64_t H, int64_t W, int64_t C,
+                                   int64_t COUT) {
+  if (H < 1 || W < 1) return nullptr;
+  for (const auto& l : kConv3HwLaunches)
+    if (l.C == C && l.COUT == COUT) return &l;
+  return nullptr;
+}
+
 // ===========================================================================
 // Stem conv of the torso (K2d): 3x3 stride-1 pad-1 at 84x84, C=4 -> 16, the
 // one conv the kernels above cannot take (K = 36; an 8-element piece would
@@ -1340,8 +1458,9 @@ struct StemGeom {
   static_assert(LDS_ROW % 8 == 0, "LDS rows must stay 16-byte aligned");
 };
 
-template <int H, int W, int WAVES, int RPW>
-__global__ __launch_bounds__(WAVES * 64) void conv3x3c4_fwd_kernel(
+template <class HW, int WAVES, int RPW>
+__device__ __forceinline__ void conv3x3c4_fwd_body(
+    const HW hw,
     const __bf16* __restrict__ in,      // (N,H,W,4) NHWC
     const __bf16* __restrict__ weight,  // (16, 36) = (cout, kh, kw, c)
     const __bf16* __restrict__ bias,    // (16), may be null
@@ -1349,6 +1468,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3c4_fwd_kernel(
     int batch) {
   using G = StemGeom;
   constexpr int C = G::C, COUT = G::COUT;
+  const int H = hw.H, W = hw.W;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* wlds = reinterpret_cast<__bf16*>(smem);
 
@@ -1435,6 +1555,23 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3c4_fwd_kernel(
   }
 }
 
+template <int H, int W, int WAVES, int RPW>
+__global__ __launch_bounds__(WAVES * 64) void conv3x3c4_fwd_kernel(
+    const __bf16* __restrict__ in, const __bf16* __restrict__ weight,
+    const __bf16* __restrict__ bias, __bf16* __restrict__ out, int batch) {
+  conv3x3c4_fwd_body<HwConst<H, W>, WAVES, RPW>(HwConst<H, W>{}, in, weight,
+                                                bias, out, batch);
+}
+
+template <int WAVES, int RPW>
+__global__ __launch_bounds__(WAVES * 64) void conv3x3c4_fwd_hw_kernel(
+    const __bf16* __restrict__ in, const __bf16* __restrict__ weight,
+    const __bf16* __restrict__ bias, __bf16* __restrict__ out, int batch,
+    int H, int W) {
+  conv3x3c4_fwd_body<HwArgs, WAVES, RPW>(HwArgs{H, W}, in, weight, bias, out,
+                                         batch);
+}
+
 // ---------------------------------------------------------------------------
 // Weight gradient of the stem conv, conv3x3p1_wrw_kernel's method:
 //   gw[co][(kh,kw,c)] = sum_m gout[m][co] * im2col(x)[m][(kh,kw,c)]
@@ -1470,14 +1607,16 @@ struct StemWrw {
   static_assert(LDS_BYTES <= 64 * 1024, "dynamic LDS limit");
 };
 
-template <int H, int W, int R>
-__global__ __launch_bounds__(256) void conv3x3c4_wrw_kernel(
+template <class HW, int R>
+__device__ __forceinline__ void conv3x3c4_wrw_body(
+    const HW hw,
     const __bf16* __restrict__ x,     // (N,H,W,4) NHWC
     const __bf16* __restrict__ gout,  // (M, 16) = NHWC grad
     float* __restrict__ gw_part,      // (mblocks, 576 + kPlanePad) fp32
     int batch, int mblocks) {
   using G = StemWrw<R>;
   constexpr int C = G::C, COUT = G::COUT;
+  const int H = hw.H, W = hw.W;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* x_t = reinterpret_cast<__bf16*>(smem);  // [ROWS][XSTRIDE]
   __bf16* g_t = x_t + G::ROWS * G::XSTRIDE;       // [ROWS][GSTRIDE]
@@ -1580,6 +1719,22 @@ __global__ __launch_bounds__(256) void conv3x3c4_wrw_kernel(
   }
 }
 
+template <int H, int W, int R>
+__global__ __launch_bounds__(256) void conv3x3c4_wrw_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ gout,
+    float* __restrict__ gw_part, int batch, int mblocks) {
+  conv3x3c4_wrw_body<HwConst<H, W>, R>(HwConst<H, W>{}, x, gout, gw_part,
+                                       batch, mblocks);
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void conv3x3c4_wrw_hw_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ gout,
+    float* __restrict__ gw_part, int batch, int mblocks, int H, int W) {
+  conv3x3c4_wrw_body<HwArgs, R>(HwArgs{H, W}, x, gout, gw_part, batch,
+                                mblocks);
+}
+
 // the stem's own one-entry table (it does not go through kConv3Launches)
 struct StemLaunch {
   int H, W, C, COUT;
@@ -1616,6 +1771,43 @@ static const StemLaunch kStemLaunches[] = {
 const StemLaunch* find_stem(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   for (const auto& l : kStemLaunches)
     if (l.H == H && l.W == W && l.C == C && l.COUT == COUT) return &l;
+  return nullptr;
+}
+
+// the stem's run-time entry (the _hw bindings): StemLaunch's fields, H and
+// W as two trailing kernel arguments
+struct StemHwLaunch {
+  int C, COUT;
+  void (*fwd)(const __bf16*, const __bf16*, const __bf16*, __bf16*, int, int,
+              int);
+  int lds_bytes, waves, rpw;
+  void (*wrw)(const __bf16*, const __bf16*, float*, int, int, int, int);
+  int wrw_lds_bytes, wrw_rows;
+  void (*colsum)(const __bf16*, int64_t, float*);
+};
+
+template <int WAVES, int RPW, int WRW_R>
+StemHwLaunch make_stem_hw() {
+  StemHwLaunch l{};
+  l.C = StemGeom::C; l.COUT = StemGeom::COUT;
+  l.fwd = conv3x3c4_fwd_hw_kernel<WAVES, RPW>;
+  l.lds_bytes = StemGeom::LDS_BYTES;
+  l.waves = WAVES;
+  l.rpw = RPW;
+  l.wrw = conv3x3c4_wrw_hw_kernel<WRW_R>;
+  l.wrw_lds_bytes = StemWrw<WRW_R>::LDS_BYTES;
+  l.wrw_rows = 32 * WRW_R;
+  l.colsum = colsum_bf16_kernel<StemGeom::COUT>;
+  return l;
+}
+
+static const StemHwLaunch kStemHwLaunches[] = {
+    make_stem_hw<8, 32, 1>(),  // the table entry's tile shapes
+};
+
+const StemHwLaunch* find_stem_hw(int64_t C, int64_t COUT) {
+  for (const auto& l : kStemHwLaunches)
+    if (l.C == C && l.COUT == COUT) return &l;
   return nullptr;
 }
 
@@ -2069,6 +2261,33 @@ int wrw_resident_blocks(const StemLaunch& L) {
                          L.wrw_lds_bytes, "conv3x3c4_wrw");
 }
 
+// the run-time kernels have their own figures: their register counts are
+// not the table kernels'
+int wrw_resident_blocks(const Conv3HwLaunch& L) {
+  static std::atomic<int> cache[std::size(kConv3HwLaunches)][kMaxDevices] = {};
+  return resident_blocks(cache[&L - kConv3HwLaunches], (const void*)L.wrw,
+                         L.wrw_lds_bytes, "conv3x3p1_wrw (run-time H, W)");
+}
+
+int wrw_resident_blocks(const StemHwLaunch& L) {
+  static std::atomic<int> cache[std::size(kStemHwLaunches)][kMaxDevices] = {};
+  return resident_blocks(cache[&L - kStemHwLaunches], (const void*)L.wrw,
+                         L.wrw_lds_bytes, "conv3x3c4_wrw_hw");
+}
+
+// m-grid of an ordered weight gradient from its pass count, the smallest of
+// three: a block should meet at least 8 passes, so the plane it writes (and
+// the fold reads back) stays well below the input bytes it streams; all
+// planes together stay within 16 MiB; and no more blocks than are resident
+// at once (a second, part-filled round of blocks would only add planes)
+int wrw_m_grid(int n_pass, int64_t plane_bytes, int resident) {
+  int mb = (n_pass + 7) / 8;
+  const int mb_cap = (int)(((int64_t)16 << 20) / plane_bytes);
+  if (mb > mb_cap) mb = mb_cap;
+  if (mb > resident) mb = resident;
+  return mb < 1 ? 1 : mb;
+}
+
 void launch_wrw_reduce(const torch::Tensor& part, int mb,
                        const torch::Tensor& b_part, int64_t COUT,
                        torch::Tensor& gw_ws, torch::Tensor& gb_ws, bool bias);
@@ -2132,7 +2351,7 @@ void launch_conv3(const torch::Tensor& in, const __bf16* w,
                   const __bf16* flip_from, const torch::Tensor& bias,
                   const torch::Tensor& residual, const torch::Tensor& mask,
                   const torch::Tensor& out, int64_t COUT, bool relu_in,
-                  bool relu_out, const Conv3Labels& lb) {
+                  bool relu_out, bool any_hw, const Conv3Labels& lb) {
   const int64_t N = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
   check_nhwc(in, kBF16, N, C, H, W, lb.in);
   check_nhwc(out, kBF16, N, COUT, H, W, lb.out);
@@ -2142,9 +2361,12 @@ void launch_conv3(const torch::Tensor& in, const __bf16* w,
   TORCH_CHECK((uintptr_t)in.data_ptr() % 16 == 0, lb.in, " is misaligned");
   TORCH_CHECK((uintptr_t)w % 16 == 0, lb.in, "'s weight is misaligned");
   TORCH_CHECK((uintptr_t)out.data_ptr() % 8 == 0, lb.out, " is misaligned");
-  const Conv3Launch* L = find_conv3(H, W, C, COUT);
-  TORCH_CHECK(L, "no 3x3 pad-1 conv kernel for this geometry: ", H, "x", W, "x",
-              C, " -> ", COUT);
+  // the geometry table first, then the (C, COUT) run-time entry; any_hw
+  // (tests and the measurement) skips the table
+  const Conv3Launch* L = any_hw ? nullptr : find_conv3(H, W, C, COUT);
+  const Conv3HwLaunch* R = L ? nullptr : find_conv3_hw(H, W, C, COUT);
+  TORCH_CHECK(L || R, "no 3x3 pad-1 conv kernel for this geometry: ", H, "x",
+              W, "x", C, " -> ", COUT);
   const int M = checked_rows(N * H * W, lb.out);
   const __bf16* bias_ptr = opt_vec(bias, COUT, lb.bias);
   // optional tensor shaped like out: undefined or empty means "none"
@@ -2164,13 +2386,20 @@ void launch_conv3(const torch::Tensor& in, const __bf16* w,
                        dim3(256), 0, cur_stream(), flip_from,
                        const_cast<__bf16*>(w), (int)COUT, (int)C);
   }
-  const int rows_per_block = L->waves * L->rpw;
+  const int rows_per_block = L ? L->waves * L->rpw : R->waves * R->rpw;
   const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(mask_ptr ? L->fn_mask : L->fn, dim3(blocks),
-                     dim3(L->waves * 64), L->lds_bytes, cur_stream(),
-                     (const __bf16*)in.data_ptr(), w, bias_ptr, res_ptr,
-                     mask_ptr, (__bf16*)out.data_ptr(), (int)N,
-                     relu_in ? 1 : 0, relu_out ? 1 : 0);
+  if (L)
+    hipLaunchKernelGGL(mask_ptr ? L->fn_mask : L->fn, dim3(blocks),
+                       dim3(L->waves * 64), L->lds_bytes, cur_stream(),
+                       (const __bf16*)in.data_ptr(), w, bias_ptr, res_ptr,
+                       mask_ptr, (__bf16*)out.data_ptr(), (int)N,
+                       relu_in ? 1 : 0, relu_out ? 1 : 0);
+  else
+    hipLaunchKernelGGL(mask_ptr ? R->fn_mask : R->fn, dim3(blocks),
+                       dim3(R->waves * 64), R->lds_bytes, cur_stream(),
+                       (const __bf16*)in.data_ptr(), w, bias_ptr, res_ptr,
+                       mask_ptr, (__bf16*)out.data_ptr(), (int)N,
+                       relu_in ? 1 : 0, relu_out ? 1 : 0, (int)H, (int)W);
 }
 
 }  // namespace
@@ -2562,22 +2791,26 @@ void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                      (int)M);
 }
 
+// a table geometry, or any H, W >= 1 at a (C, COUT) with a run-time entry
 bool conv3x3p1_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
-  return find_conv3(H, W, C, COUT) != nullptr;
+  return find_conv3(H, W, C, COUT) != nullptr ||
+         find_conv3_hw(H, W, C, COUT) != nullptr;
 }
 
 // in: (N,C,H,W) logical channels_last bf16; weight: (COUT,C,3,3) logical
 // channels_last bf16; bias: (COUT) bf16 or empty; residual: same shape and
 // layout as out, or empty; out: (N,COUT,H,W) logical channels_last bf16.
 // One launch on the current stream, no allocation, no sync (graph-safe).
+// any_hw: run the run-time H, W kernel even at a table geometry (tests and
+// tools/gpu_resconv_hw_bench.py).
 void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
                    torch::Tensor residual, torch::Tensor out, bool relu_in,
-                   bool relu_out) {
+                   bool relu_out, bool any_hw) {
   TORCH_CHECK(in.dim() == 4 && weight.dim() == 4);
   const int64_t COUT = weight.size(0);
   check_nhwc(weight, kBF16, COUT, in.size(1), 3, 3, "conv3x3p1_fwd weight");
   launch_conv3(in, (const __bf16*)weight.data_ptr(), nullptr, bias, residual,
-               torch::Tensor(), out, COUT, relu_in, relu_out,
+               torch::Tensor(), out, COUT, relu_in, relu_out, any_hw,
                {"conv3x3p1_fwd input", "conv3x3p1_fwd output",
                 "conv3x3p1_fwd bias", "conv3x3p1_fwd residual",
                 "conv3x3p1_fwd mask"});
@@ -2585,22 +2818,64 @@ void conv3x3p1_fwd(torch::Tensor in, torch::Tensor weight, torch::Tensor bias,
 
 bool conv3x3p1_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   const Conv3Launch* L = find_conv3(H, W, C, COUT);
-  return L && L->wrw;
+  if (L) return L->wrw != nullptr;
+  const Conv3HwLaunch* R = find_conv3_hw(H, W, C, COUT);
+  return R && R->wrw;
+}
+
+namespace {
+// What conv3x3p1_wrw launches for x (N,C,H,W) -> COUT: the entry (table
+// first, then run-time; any_hw skips the table), its rows per pass, M and
+// the m-grid from wrw_m_grid with that entry's residency figure. The
+// launch and the conv3x3p1_wrw_plan query both take it from here.
+struct Conv3WrwPlan {
+  const Conv3Launch* L;
+  const Conv3HwLaunch* R;
+  int rows, M, resident, mb;
+};
+
+Conv3WrwPlan plan_conv3_wrw(int64_t N, int64_t H, int64_t W, int64_t C,
+                            int64_t COUT, bool any_hw) {
+  Conv3WrwPlan p{};
+  p.L = any_hw ? nullptr : find_conv3(H, W, C, COUT);
+  p.R = p.L ? nullptr : find_conv3_hw(H, W, C, COUT);
+  TORCH_CHECK(p.L ? p.L->wrw != nullptr : p.R && p.R->wrw,
+              "no 3x3 pad-1 wrw kernel for this geometry: ", H, "x", W, "x", C,
+              " -> ", COUT);
+  p.rows = p.L ? p.L->wrw_rows : p.R->wrw_rows;
+  // the last pass's row numbers run past M by less than a pass
+  p.M = checked_rows(N * H * W + p.rows, "conv3x3p1_wrw") - p.rows;
+  p.resident = p.L ? wrw_resident_blocks(*p.L) : wrw_resident_blocks(*p.R);
+  p.mb = wrw_m_grid((p.M + p.rows - 1) / p.rows,
+                    (COUT * 9 * C + kPlanePad) * 4, p.resident);
+  return p;
+}
+}  // namespace
+
+// (m-blocks, rows per pass, resident blocks) of the conv3x3p1_wrw call on
+// an x of this shape: the launch's own plan, for the tests that pin the
+// summation order of the run-time path
+std::tuple<int64_t, int64_t, int64_t> conv3x3p1_wrw_plan(
+    int64_t N, int64_t H, int64_t W, int64_t C, int64_t COUT, bool any_hw) {
+  const Conv3WrwPlan p = plan_conv3_wrw(N, H, W, C, COUT, any_hw);
+  return {p.mb, p.rows, p.resident};
 }
 
 // x: (N,C,H,W) and gout: (N,COUT,H,W) logical channels_last bf16 (gout
 // already relu-masked); gw: (COUT, 9C) fp32 workspace, or the bf16 gradient
 // itself in (cout, kh, kw, c) memory order; gb: (COUT) of gw's dtype, or
-// empty — conv_wrw's contracts. relu_in: the conv read relu(x).
+// empty — conv_wrw's contracts. relu_in: the conv read relu(x). any_hw: as
+// conv3x3p1_fwd's. The m-grid, and with it the summation order, follows
+// the residency figure of the kernel that runs.
 void conv3x3p1_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
-                   torch::Tensor gb, bool relu_in) {
+                   torch::Tensor gb, bool relu_in, bool any_hw) {
   TORCH_CHECK(x.dim() == 4 && gout.dim() == 4,
               "conv3x3p1_wrw wants 4-D x and gout");
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int64_t COUT = gout.size(1);
-  const Conv3Launch* L = find_conv3(H, W, C, COUT);
-  TORCH_CHECK(L && L->wrw, "no 3x3 pad-1 wrw kernel for this geometry: ", H,
-              "x", W, "x", C, " -> ", COUT);
+  const Conv3WrwPlan plan = plan_conv3_wrw(N, H, W, C, COUT, any_hw);
+  const Conv3Launch* L = plan.L;
+  const Conv3HwLaunch* R = plan.R;
   check_nhwc(x, kBF16, N, C, H, W, "conv3x3p1_wrw x");
   check_nhwc(gout, kBF16, N, COUT, H, W, "conv3x3p1_wrw gout (x's batch)");
   TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
@@ -2617,29 +2892,21 @@ void conv3x3p1_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
               " elements, got ", gw.numel());
   const bool bias = gb.defined() && gb.numel() > 0;
   if (bias) check_rows(gb, gw.scalar_type(), {COUT}, "conv3x3p1_wrw gb");
-  // the last pass's row numbers run past M by less than a pass
-  const int M = checked_rows(N * H * W + L->wrw_rows, "conv3x3p1_wrw") -
-                L->wrw_rows;
-  const int n_pass = (M + L->wrw_rows - 1) / L->wrw_rows;
-  // m-grid from M, the smallest of three: a block should meet at least 8
-  // passes, so the plane it writes (and the fold reads back) stays well
-  // below the input bytes it streams; all planes together stay within
-  // 16 MiB; and no more blocks than are resident at once (a second,
-  // part-filled round of blocks would only add planes)
-  const int64_t plane_bytes = (n_elem + kPlanePad) * 4;
-  int mb = (n_pass + 7) / 8;
-  const int mb_cap = (int)(((int64_t)16 << 20) / plane_bytes);
-  if (mb > mb_cap) mb = mb_cap;
-  const int resident = wrw_resident_blocks(*L);
-  if (mb > resident) mb = resident;
-  if (mb < 1) mb = 1;
+  const int M = plan.M, mb = plan.mb;
   const auto f32 = gw.options().dtype(torch::kFloat32);
   auto part = torch::empty({(int64_t)mb, n_elem + kPlanePad}, f32);
-  hipLaunchKernelGGL(L->wrw, dim3(mb), dim3(256), L->wrw_lds_bytes,
-                     cur_stream(), (const __bf16*)x.data_ptr(),
-                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
-                     (int)N, mb, relu_in ? 1 : 0);
-  launch_wrw_fold(part, mb, gout, M, COUT, L->colsum, gw, gb, bias);
+  if (L)
+    hipLaunchKernelGGL(L->wrw, dim3(mb), dim3(256), L->wrw_lds_bytes,
+                       cur_stream(), (const __bf16*)x.data_ptr(),
+                       (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                       (int)N, mb, relu_in ? 1 : 0);
+  else
+    hipLaunchKernelGGL(R->wrw, dim3(mb), dim3(256), R->wrw_lds_bytes,
+                       cur_stream(), (const __bf16*)x.data_ptr(),
+                       (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                       (int)N, mb, relu_in ? 1 : 0, (int)H, (int)W);
+  launch_wrw_fold(part, mb, gout, M, COUT, L ? L->colsum : R->colsum, gw, gb,
+                  bias);
 }
 
 // Input gradient of the conv (x -> out, weight (COUT,C,3,3)) through the
@@ -2648,9 +2915,10 @@ void conv3x3p1_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
 // workspace (overwritten with W'); gx: (N,C,H,W); mask_x: empty, or the
 // conv's input x — gx is then zeroed where x <= 0 (relu_in backward). All
 // logical channels_last bf16. Two launches, no allocation (graph-safe).
+// any_hw: as conv3x3p1_fwd's.
 void conv3x3p1_dgrad(torch::Tensor gout, torch::Tensor weight,
                      torch::Tensor w_flip_ws, torch::Tensor gx,
-                     torch::Tensor mask_x) {
+                     torch::Tensor mask_x, bool any_hw) {
   TORCH_CHECK(gout.dim() == 4 && weight.dim() == 4 && gx.dim() == 4,
               "conv3x3p1_dgrad wants 4-D gout, weight and gx");
   const int64_t COUT = weight.size(0), C = weight.size(1);
@@ -2661,7 +2929,7 @@ void conv3x3p1_dgrad(torch::Tensor gout, torch::Tensor weight,
   check_rows(w_flip_ws, kBF16, {weight.numel()}, "conv3x3p1_dgrad w_flip_ws");
   launch_conv3(gout, (const __bf16*)w_flip_ws.data_ptr(),
                (const __bf16*)weight.data_ptr(), torch::Tensor(),
-               torch::Tensor(), mask_x, gx, C, false, false,
+               torch::Tensor(), mask_x, gx, C, false, false, any_hw,
                {"conv3x3p1_dgrad gout", "conv3x3p1_dgrad gx",
                 "conv3x3p1_dgrad bias", "conv3x3p1_dgrad residual",
                 "conv3x3p1_dgrad mask_x"});
@@ -2676,57 +2944,162 @@ bool conv3x3c4_wrw_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
   return L && L->wrw;
 }
 
+// the run-time stem kernels: any H, W >= 1 at this (C, COUT)
+bool conv3x3c4_hw_supported(int64_t C, int64_t COUT) {
+  return find_stem_hw(C, COUT) != nullptr;
+}
+
 namespace {
-// the stem entry for x (N,C,H,W) and COUT, or an error that names the
-// argument the geometry fails on
-const StemLaunch& stem_for(const torch::Tensor& x, int64_t COUT,
-                           const char* x_name, const char* cout_name) {
+// The stem entry of a call: `table` (conv3x3c4_fwd / _wrw) takes
+// kStemLaunches and rejects every other geometry; otherwise (the _hw
+// bindings) the (C, COUT) run-time entry at any H, W >= 1, table geometry
+// included. An error names the argument the geometry fails on.
+struct StemPick {
+  const StemLaunch* L;
+  const StemHwLaunch* R;
+  int waves() const { return L ? L->waves : R->waves; }
+  int rpw() const { return L ? L->rpw : R->rpw; }
+  int wrw_rows() const { return L ? L->wrw_rows : R->wrw_rows; }
+};
+
+StemPick stem_for(const torch::Tensor& x, int64_t COUT, bool table,
+                  const std::string& x_name, const std::string& cout_name) {
   const int64_t C = x.size(1), H = x.size(2), W = x.size(3);
-  const StemLaunch* L = find_stem(H, W, C, COUT);
-  if (L) return *L;
   bool x_known = false;
-  for (const auto& l : kStemLaunches)
-    x_known = x_known || (l.H == H && l.W == W && l.C == C);
-  TORCH_CHECK(x_known, x_name, ": no stem conv kernel for ", H, "x", W, "x", C);
-  TORCH_CHECK(false, cout_name, ": no stem conv kernel for ", H, "x", W, "x",
-              C, " -> ", COUT);
-  return kStemLaunches[0];
+  if (table) {
+    if (const StemLaunch* L = find_stem(H, W, C, COUT)) return {L, nullptr};
+    for (const auto& l : kStemLaunches)
+      x_known = x_known || (l.H == H && l.W == W && l.C == C);
+  } else {
+    if (H >= 1 && W >= 1)
+      if (const StemHwLaunch* R = find_stem_hw(C, COUT)) return {nullptr, R};
+    for (const auto& l : kStemHwLaunches)
+      x_known = x_known || (H >= 1 && W >= 1 && l.C == C);
+  }
+  // the table bindings keep their wording
+  const char* no = table ? ": no stem conv kernel for "
+                         : ": no stem conv kernel for this geometry: ";
+  TORCH_CHECK(x_known, x_name, no, H, "x", W, "x", C);
+  TORCH_CHECK(false, cout_name, no, H, "x", W, "x", C, " -> ", COUT);
+  return {nullptr, nullptr};
+}
+
+// rows per pass, M and m-grid of a stem weight gradient on entry S:
+// conv3x3p1_wrw's three rules with the residency figure of the kernel that
+// runs. The launch and the conv3x3c4_wrw_plan query both take it from here.
+struct StemWrwPlan {
+  int rows, M, resident, mb;
+};
+
+StemWrwPlan plan_stem_wrw(const StemPick& S, int64_t N, int64_t H, int64_t W,
+                          const char* who) {
+  StemWrwPlan p{};
+  p.rows = S.wrw_rows();
+  // the last pass's row numbers run past M by less than a pass
+  p.M = checked_rows(N * H * W + p.rows, who) - p.rows;
+  p.resident = S.L ? wrw_resident_blocks(*S.L) : wrw_resident_blocks(*S.R);
+  p.mb = wrw_m_grid((p.M + p.rows - 1) / p.rows,
+                    (StemGeom::COUT * StemGeom::K + kPlanePad) * 4, p.resident);
+  return p;
+}
+
+// who: the binding's name, the prefix of every argument name in an error
+void stem_fwd(const torch::Tensor& x, const torch::Tensor& weight,
+              const torch::Tensor& bias, const torch::Tensor& out, bool table,
+              const std::string& who) {
+  TORCH_CHECK(x.dim() == 4 && weight.dim() == 4, who,
+              " wants 4-D x and weight");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t COUT = weight.size(0);
+  const std::string xn = who + " x", wn = who + " weight", on = who + " out",
+                    bn = who + " bias";
+  const StemPick S = stem_for(x, COUT, table, xn, wn);
+  check_nhwc(x, kBF16, N, C, H, W, xn.c_str());
+  check_nhwc(weight, kBF16, COUT, C, 3, 3, wn.c_str());
+  check_nhwc(out, kBF16, N, COUT, H, W, on.c_str());
+  TORCH_CHECK(out.data_ptr() != x.data_ptr(), on, " must not alias x");
+  // 8-byte pieces of x, weight and out
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 8 == 0, xn, " is misaligned");
+  TORCH_CHECK((uintptr_t)weight.data_ptr() % 8 == 0, wn, " is misaligned");
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 8 == 0, on, " is misaligned");
+  const __bf16* bias_ptr = opt_vec(bias, COUT, bn.c_str());
+  const int M = checked_rows(N * H * W, on.c_str());
+  if (M == 0) return;
+  const int rows_per_block = S.waves() * S.rpw();
+  const int blocks = (M + rows_per_block - 1) / rows_per_block;
+  if (S.L)
+    hipLaunchKernelGGL(S.L->fwd, dim3(blocks), dim3(S.L->waves * 64),
+                       S.L->lds_bytes, cur_stream(),
+                       (const __bf16*)x.data_ptr(),
+                       (const __bf16*)weight.data_ptr(), bias_ptr,
+                       (__bf16*)out.data_ptr(), (int)N);
+  else
+    hipLaunchKernelGGL(S.R->fwd, dim3(blocks), dim3(S.R->waves * 64),
+                       S.R->lds_bytes, cur_stream(),
+                       (const __bf16*)x.data_ptr(),
+                       (const __bf16*)weight.data_ptr(), bias_ptr,
+                       (__bf16*)out.data_ptr(), (int)N, (int)H, (int)W);
+}
+
+void stem_wrw(const torch::Tensor& x, const torch::Tensor& gout,
+              torch::Tensor& gw, torch::Tensor& gb, bool table,
+              const std::string& who) {
+  TORCH_CHECK(x.dim() == 4 && gout.dim() == 4, who, " wants 4-D x and gout");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t COUT = gout.size(1);
+  const std::string xn = who + " x", gn = who + " gout", gwn = who + " gw",
+                    gbn = who + " gb";
+  const StemPick S = stem_for(x, COUT, table, xn, gn);
+  check_nhwc(x, kBF16, N, C, H, W, xn.c_str());
+  check_nhwc(gout, kBF16, N, COUT, H, W, (gn + " (x's batch)").c_str());
+  // 8-byte pieces of x, 16-byte pieces of gout, 16-byte stores to gw
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 8 == 0, xn, " is misaligned");
+  TORCH_CHECK((uintptr_t)gout.data_ptr() % 16 == 0, gn, " is misaligned");
+  TORCH_CHECK(gw.defined(), gwn, " is undefined");
+  const bool bf16_out = gw.scalar_type() == kBF16;
+  check_dev(gw, bf16_out ? kBF16 : torch::kFloat32, gwn.c_str());
+  TORCH_CHECK(gw.is_contiguous() ||
+                  (gw.dim() == 4 &&
+                   gw.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              gwn, " must be dense in (cout, kh, kw, c) order");
+  const int64_t n_elem = COUT * 9 * C;
+  TORCH_CHECK(gw.numel() == n_elem, gwn, " must hold ", n_elem,
+              " elements, got ", gw.numel());
+  TORCH_CHECK((uintptr_t)gw.data_ptr() % 16 == 0, gwn, " is misaligned");
+  const bool bias = gb.defined() && gb.numel() > 0;
+  if (bias) check_rows(gb, gw.scalar_type(), {COUT}, gbn.c_str());
+  const StemWrwPlan plan = plan_stem_wrw(S, N, H, W, xn.c_str());
+  const int M = plan.M, mb = plan.mb;
+  const auto f32 = gw.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)mb, n_elem + kPlanePad}, f32);
+  if (S.L)
+    hipLaunchKernelGGL(S.L->wrw, dim3(mb), dim3(256), S.L->wrw_lds_bytes,
+                       cur_stream(), (const __bf16*)x.data_ptr(),
+                       (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                       (int)N, mb);
+  else
+    hipLaunchKernelGGL(S.R->wrw, dim3(mb), dim3(256), S.R->wrw_lds_bytes,
+                       cur_stream(), (const __bf16*)x.data_ptr(),
+                       (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                       (int)N, mb, (int)H, (int)W);
+  launch_wrw_fold(part, mb, gout, M, COUT, S.L ? S.L->colsum : S.R->colsum,
+                  gw, gb, bias);
 }
 }  // namespace
 
 // x: (N,4,84,84) logical channels_last bf16; weight: (16,4,3,3) logical
 // channels_last bf16; bias: (16) bf16 or empty; out: (N,16,84,84) logical
 // channels_last bf16. One launch on the current stream, no allocation, no
-// sync (graph-safe).
+// sync (graph-safe). The table kernel: 84x84 only.
 void conv3x3c4_fwd(torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
                    torch::Tensor out) {
-  TORCH_CHECK(x.dim() == 4 && weight.dim() == 4,
-              "conv3x3c4_fwd wants 4-D x and weight");
-  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int64_t COUT = weight.size(0);
-  const StemLaunch& L =
-      stem_for(x, COUT, "conv3x3c4_fwd x", "conv3x3c4_fwd weight");
-  check_nhwc(x, kBF16, N, C, H, W, "conv3x3c4_fwd x");
-  check_nhwc(weight, kBF16, COUT, C, 3, 3, "conv3x3c4_fwd weight");
-  check_nhwc(out, kBF16, N, COUT, H, W, "conv3x3c4_fwd out");
-  TORCH_CHECK(out.data_ptr() != x.data_ptr(),
-              "conv3x3c4_fwd out must not alias x");
-  // 8-byte pieces of x, weight and out
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 8 == 0,
-              "conv3x3c4_fwd x is misaligned");
-  TORCH_CHECK((uintptr_t)weight.data_ptr() % 8 == 0,
-              "conv3x3c4_fwd weight is misaligned");
-  TORCH_CHECK((uintptr_t)out.data_ptr() % 8 == 0,
-              "conv3x3c4_fwd out is misaligned");
-  const __bf16* bias_ptr = opt_vec(bias, COUT, "conv3x3c4_fwd bias");
-  const int M = checked_rows(N * H * W, "conv3x3c4_fwd out");
-  if (M == 0) return;
-  const int rows_per_block = L.waves * L.rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(L.fwd, dim3(blocks), dim3(L.waves * 64), L.lds_bytes,
-                     cur_stream(), (const __bf16*)x.data_ptr(),
-                     (const __bf16*)weight.data_ptr(), bias_ptr,
-                     (__bf16*)out.data_ptr(), (int)N);
+  stem_fwd(x, weight, bias, out, true, "conv3x3c4_fwd");
+}
+
+// conv3x3c4_fwd at any H, W >= 1 (84x84 included) on the run-time kernel
+void conv3x3c4_fwd_hw(torch::Tensor x, torch::Tensor weight,
+                      torch::Tensor bias, torch::Tensor out) {
+  stem_fwd(x, weight, bias, out, false, "conv3x3c4_fwd_hw");
 }
 
 // x: (N,4,84,84) and gout: (N,16,84,84) logical channels_last bf16; gw:
@@ -2736,53 +3109,29 @@ void conv3x3c4_fwd(torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
 // partials of the fold).
 void conv3x3c4_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
                    torch::Tensor gb) {
-  TORCH_CHECK(x.dim() == 4 && gout.dim() == 4,
-              "conv3x3c4_wrw wants 4-D x and gout");
-  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int64_t COUT = gout.size(1);
-  const StemLaunch& L =
-      stem_for(x, COUT, "conv3x3c4_wrw x", "conv3x3c4_wrw gout");
-  check_nhwc(x, kBF16, N, C, H, W, "conv3x3c4_wrw x");
-  check_nhwc(gout, kBF16, N, COUT, H, W, "conv3x3c4_wrw gout (x's batch)");
-  // 8-byte pieces of x, 16-byte pieces of gout, 16-byte stores to gw
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 8 == 0,
-              "conv3x3c4_wrw x is misaligned");
-  TORCH_CHECK((uintptr_t)gout.data_ptr() % 16 == 0,
-              "conv3x3c4_wrw gout is misaligned");
-  TORCH_CHECK(gw.defined(), "conv3x3c4_wrw gw is undefined");
-  const bool bf16_out = gw.scalar_type() == kBF16;
-  check_dev(gw, bf16_out ? kBF16 : torch::kFloat32, "conv3x3c4_wrw gw");
-  TORCH_CHECK(gw.is_contiguous() ||
-                  (gw.dim() == 4 &&
-                   gw.is_contiguous(at::MemoryFormat::ChannelsLast)),
-              "conv3x3c4_wrw gw must be dense in (cout, kh, kw, c) order");
-  const int64_t n_elem = COUT * 9 * C;
-  TORCH_CHECK(gw.numel() == n_elem, "conv3x3c4_wrw gw must hold ", n_elem,
-              " elements, got ", gw.numel());
-  TORCH_CHECK((uintptr_t)gw.data_ptr() % 16 == 0,
-              "conv3x3c4_wrw gw is misaligned");
-  const bool bias = gb.defined() && gb.numel() > 0;
-  if (bias) check_rows(gb, gw.scalar_type(), {COUT}, "conv3x3c4_wrw gb");
-  // the last pass's row numbers run past M by less than a pass
-  const int M =
-      checked_rows(N * H * W + L.wrw_rows, "conv3x3c4_wrw x") - L.wrw_rows;
-  const int n_pass = (M + L.wrw_rows - 1) / L.wrw_rows;
-  // m-grid: conv3x3p1_wrw's three rules (a block per 8 passes, 16 MiB of
-  // planes, no more blocks than are resident at once)
-  const int64_t plane_bytes = (n_elem + kPlanePad) * 4;
-  int mb = (n_pass + 7) / 8;
-  const int mb_cap = (int)(((int64_t)16 << 20) / plane_bytes);
-  if (mb > mb_cap) mb = mb_cap;
-  const int resident = wrw_resident_blocks(L);
-  if (mb > resident) mb = resident;
-  if (mb < 1) mb = 1;
-  const auto f32 = gw.options().dtype(torch::kFloat32);
-  auto part = torch::empty({(int64_t)mb, n_elem + kPlanePad}, f32);
-  hipLaunchKernelGGL(L.wrw, dim3(mb), dim3(256), L.wrw_lds_bytes, cur_stream(),
-                     (const __bf16*)x.data_ptr(),
-                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
-                     (int)N, mb);
-  launch_wrw_fold(part, mb, gout, M, COUT, L.colsum, gw, gb, bias);
+  stem_wrw(x, gout, gw, gb, true, "conv3x3c4_wrw");
+}
+
+// (m-blocks, rows per pass, resident blocks) of the stem weight gradient on
+// N images of HxW: conv3x3c4_wrw_hw's plan (hw) or conv3x3c4_wrw's
+std::tuple<int64_t, int64_t, int64_t> conv3x3c4_wrw_plan(int64_t N, int64_t H,
+                                                         int64_t W, bool hw) {
+  const StemLaunch* L =
+      hw ? nullptr : find_stem(H, W, StemGeom::C, StemGeom::COUT);
+  const StemHwLaunch* R =
+      hw && H >= 1 && W >= 1 ? find_stem_hw(StemGeom::C, StemGeom::COUT)
+                             : nullptr;
+  TORCH_CHECK(L || R, "conv3x3c4_wrw_plan: no stem conv kernel for this "
+              "geometry: ", H, "x", W);
+  const StemWrwPlan p =
+      plan_stem_wrw(StemPick{L, R}, N, H, W, "conv3x3c4_wrw_plan");
+  return {p.mb, p.rows, p.resident};
+}
+
+// conv3x3c4_wrw at any H, W >= 1 (84x84 included) on the run-time kernel
+void conv3x3c4_wrw_hw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
+                      torch::Tensor gb) {
+  stem_wrw(x, gout, gw, gb, false, "conv3x3c4_wrw_hw");
 }
 
 bool maxpool3x3s2_supported(int64_t H, int64_t W, int64_t C) {
@@ -2877,17 +3226,25 @@ void register_conv(pybind11::module_& m) {
   m.def("linear_relu", &linear_relu,
         "fused Linear+bias+ReLU fwd (own MFMA GEMM, LDS-staged W)");
   m.def("linear_relu_supported", &linear_relu_supported);
+  namespace py = pybind11;
   m.def("conv3x3p1_fwd", &conv3x3p1_fwd,
         "MFMA 3x3 s1 pad-1 NHWC bf16 conv fwd (+relu_in, bias, residual, "
-        "relu_out)");
+        "relu_out); any_hw forces the run-time H, W kernel",
+        py::arg("input"), py::arg("weight"), py::arg("bias"),
+        py::arg("residual"), py::arg("out"), py::arg("relu_in"),
+        py::arg("relu_out"), py::arg("any_hw") = false);
   m.def("conv3x3p1_supported", &conv3x3p1_supported);
   m.def("conv3x3p1_wrw", &conv3x3p1_wrw,
         "MFMA 3x3 s1 pad-1 weight-grad (+relu_in); gw/gb are fp32 workspaces "
-        "or bf16 grads");
+        "or bf16 grads",
+        py::arg("x"), py::arg("gout"), py::arg("gw"), py::arg("gb"),
+        py::arg("relu_in"), py::arg("any_hw") = false);
   m.def("conv3x3p1_wrw_supported", &conv3x3p1_wrw_supported);
   m.def("conv3x3p1_dgrad", &conv3x3p1_dgrad,
         "3x3 s1 pad-1 input-grad: weight flip + the forward kernel at the "
-        "mirrored geometry (+relu_in mask in the epilogue)");
+        "mirrored geometry (+relu_in mask in the epilogue)",
+        py::arg("gout"), py::arg("weight"), py::arg("w_flip_ws"),
+        py::arg("gx"), py::arg("mask_x"), py::arg("any_hw") = false);
   m.def("conv3x3c4_fwd", &conv3x3c4_fwd,
         "MFMA 3x3 s1 pad-1 NHWC bf16 stem conv fwd (84x84, C=4 -> 16; bias)");
   m.def("conv3x3c4_supported", &conv3x3c4_supported);
@@ -2895,6 +3252,18 @@ void register_conv(pybind11::module_& m) {
         "MFMA stem-conv weight-grad, ordered planes; gw/gb are fp32 "
         "workspaces or bf16 grads");
   m.def("conv3x3c4_wrw_supported", &conv3x3c4_wrw_supported);
+  m.def("conv3x3c4_fwd_hw", &conv3x3c4_fwd_hw,
+        "conv3x3c4_fwd at any H, W >= 1: the run-time H, W stem kernel");
+  m.def("conv3x3c4_wrw_hw", &conv3x3c4_wrw_hw,
+        "conv3x3c4_wrw at any H, W >= 1: the run-time H, W stem kernel");
+  m.def("conv3x3c4_hw_supported", &conv3x3c4_hw_supported);
+  m.def("conv3x3p1_wrw_plan", &conv3x3p1_wrw_plan,
+        "(m-blocks, rows per pass, resident blocks) of a conv3x3p1_wrw call",
+        py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"),
+        py::arg("COUT"), py::arg("any_hw") = false);
+  m.def("conv3x3c4_wrw_plan", &conv3x3c4_wrw_plan,
+        "(m-blocks, rows per pass, resident blocks) of a stem wrw call",
+        py::arg("N"), py::arg("H"), py::arg("W"), py::arg("hw"));
   m.def("maxpool3x3s2_fwd", &maxpool3x3s2_fwd,
         "NHWC bf16 max-pool 3x3 s2 pad-1 fwd; uint8 tap plane, or none when "
         "idx is empty");
