@@ -32,6 +32,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..config import Config
 from ..models import BaseAgent
+from ..models.base_agent import ImpalaResNet
 from ..replay import FifoReplay
 from .common import LearnerBase
 
@@ -114,6 +115,19 @@ class ImpalaLearner(LearnerBase):
     def push_trajectories(self, cols: Dict[str, torch.Tensor]):
         self.replay.push(cols)
 
+    def _net_takes_u8(self) -> bool:
+        """DRL_STEM_U8 on and every node fed by graph input 0 is an
+        ImpalaResNet: the uint8 frames go to the net as they are."""
+        if not ops._gate("DRL_STEM_U8", ops._STEM_U8_DEFAULT):
+            return False
+        net = self.net
+        if not isinstance(net, BaseAgent):
+            return False
+        takers = [n for n in net.node_order
+                  if 0 in [int(i) for i in net.cfg[n].get("input", [])]]
+        return bool(takers) and all(
+            isinstance(net.nodes[n], ImpalaResNet) for n in takers)
+
     # -- train -----------------------------------------------------------
     def _fwd_bwd(self, data) -> Dict[str, torch.Tensor]:
         """Forward + V-trace + fused loss + backward (grads left in the
@@ -123,7 +137,9 @@ class ImpalaLearner(LearnerBase):
         B = data["not_done"].shape[0]
         states = data["states"].to(self.device, non_blocking=True)
         flat = states.reshape(B * (T + 1), *states.shape[2:])
-        if cuda:
+        if cuda and self._net_takes_u8():
+            x = flat  # the torso's first conv dequantises in its kernels
+        elif cuda:
             x = ops.dequant_frames_nhwc(flat)
         else:
             x = ops.dequant_frames(flat, torch.float32)

@@ -379,6 +379,33 @@ def _stem_ok(x: torch.Tensor, conv: nn.Conv2d) -> bool:
                                     w.shape[0])
 
 
+def _stem_u8_ok(x: torch.Tensor, conv: nn.Module) -> bool:
+    """Stem conv straight from uint8 frames (ops/hip/conv_mfma.hip
+    conv3x3c4_u8_*_kernel): CUDA uint8 contiguous (N, 4, H, W) input into the
+    plain 3x3 stride-1 pad-1 conv, bf16 channels_last weight on an 8-byte
+    boundary, a geometry the kernels take; gate DRL_STEM_U8 ('1' on, '0' or
+    unset off: ops._STEM_U8_DEFAULT, profiles/r11_stem_u8.md)."""
+    if not isinstance(conv, nn.Conv2d):
+        return False
+    w = conv.weight
+    if tuple(w.shape[2:]) != (3, 3) or conv.stride != (1, 1) \
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) \
+            or conv.groups != 1 or conv.padding_mode != "zeros":
+        return False
+    if not (x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4
+            and x.is_contiguous()):
+        return False
+    if w.dtype != torch.bfloat16 or w.data_ptr() % 8 \
+            or not w.is_contiguous(memory_format=torch.channels_last):
+        return False
+    from .. import ops as _ops
+
+    if not _ops._gate("DRL_STEM_U8", _ops._STEM_U8_DEFAULT):
+        return False
+    return x.shape[1] == w.shape[1] and _ops.stem_conv_u8_supported(
+        x.shape[2], x.shape[3], w.shape[1], w.shape[0])
+
+
 def _pool_ok(x: torch.Tensor, pool: nn.MaxPool2d) -> bool:
     """Own max-pool path (ops/hip/conv_mfma.hip maxpool3x3s2_*_kernel):
     kernel 3, stride 2, padding 1, dilation 1, floor mode; CUDA bf16
@@ -442,7 +469,12 @@ class ImpalaResNet(nn.Module):
     ordered weight gradient: with it every parameter's gradient is
     reproducible) when DRL_OWN_STEM=1; unset or '0' it stays in torch. The
     three gates are independent and are read per layer. The final
-    ReLU+flatten stays in torch."""
+    ReLU+flatten stays in torch.
+
+    A CUDA uint8 (N, 4, H, W) input (replay frames) is taken as well: with
+    DRL_STEM_U8=1 the first conv reads it through ops.fused_stem_conv3x3_u8
+    (dequantised inside the kernels, no bf16 copy of the batch); otherwise it
+    goes through ops.dequant_frames_nhwc first."""
 
     def __init__(self, cfg: Dict[str, Any]):
         super().__init__()
@@ -460,6 +492,19 @@ class ImpalaResNet(nn.Module):
         self.body = nn.Sequential(*sections)
 
     def forward(self, x):
+        first = 0
+        if x.is_cuda and x.dtype == torch.uint8:
+            from .. import ops as _ops
+
+            # replay frames as they are: the first conv reads them directly
+            # when DRL_STEM_U8 allows, otherwise they are dequantised to
+            # channels_last bf16 here and take the path below
+            if _stem_u8_ok(x, self.body[0]):
+                x = _ops.fused_stem_conv3x3_u8(x, self.body[0].weight,
+                                               self.body[0].bias)
+                first = 1
+            else:
+                x = _ops.dequant_frames_nhwc(x).to(next(self.parameters()).dtype)
         if x.is_cuda and x.dtype == torch.bfloat16:
             from .. import ops as _ops
 
@@ -467,7 +512,7 @@ class ImpalaResNet(nn.Module):
             # independent, and a layer nothing claims runs as nn.Sequential
             # would run it
             y = x
-            for layer in self.body:
+            for layer in self.body[first:]:
                 if isinstance(layer, nn.Conv2d) and _stem_ok(y, layer):
                     y = _ops.fused_stem_conv3x3(y, layer.weight, layer.bias)
                 elif isinstance(layer, nn.Conv2d) and _resconv_ok(y, layer):

@@ -591,6 +591,81 @@ def fused_stem_conv3x3(x, weight, bias):
     return torch_ref.conv3x3_res(x, weight, bias)
 
 
+# ---------------------------------------------------------------------------
+# K2e — the same conv fed with the replay's uint8 (N, 4, H, W) frames as they
+# are: no bf16 NHWC copy of the batch is written, kept or read back
+# ---------------------------------------------------------------------------
+
+
+def stem_conv_u8_supported(H, W, C, COUT) -> bool:
+    """C=4 -> 16 at every H >= 1 and every W whose three-row band fits the
+    kernels' LDS budget."""
+    ext = hip_ext(required=False)
+    return ext is not None and bool(
+        ext.conv3x3c4_u8_supported(H, W, C, COUT))
+
+
+# default of DRL_STEM_U8 (read by models/base_agent.py and algos/impala.py).
+# Off: the existing tests pin the launches of the step with the environment
+# unset. The A/B in profiles/r11_stem_u8.md, both with DRL_OWN_STEM=1: medians
+# 3.787 (gate on) vs 3.975 ms/step for the parent, spreads 0.004 / 0.003 ->
+# faster by r06's rule (0.188 > 0.012); both gates unset 4.419 vs 4.420.
+_STEM_U8_DEFAULT = False
+
+
+class _FusedStemConvU8Fn(torch.autograd.Function):
+    """Forward on conv3x3c4_u8_fwd_kernel; saves the uint8 frames only (the
+    replay batch is data: no bf16 copy is kept for the backward, and the
+    frames get no gradient). Backward: conv3x3c4_u8_wrw_kernel and the
+    ordered fold write the bf16 weight and bias gradients directly; the bias
+    gradient comes out of the weight gradient's MFMAs."""
+
+    @staticmethod
+    def forward(ctx, frames, weight, bias):
+        ext = hip_ext()
+        N, _, H, W = frames.shape
+        out = torch.empty(
+            N, weight.shape[0], H, W, dtype=torch.bfloat16,
+            device=frames.device, memory_format=torch.channels_last,
+        )
+        ext.conv3x3c4_u8_fwd(
+            frames, weight,
+            bias if bias is not None
+            else torch.empty(0, device=frames.device, dtype=torch.bfloat16),
+            out)
+        ctx.save_for_backward(frames)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (frames,) = ctx.saved_tensors
+        need_w = ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_w or need_b):
+            return None, None, None
+        if not gout.is_contiguous(memory_format=torch.channels_last):
+            gout = gout.contiguous(memory_format=torch.channels_last)
+        COUT, C = gout.shape[1], frames.shape[1]
+        # (COUT, 36) in (kh, kw, c) order is the channels_last layout
+        gw = torch.empty(COUT, 3, 3, C, dtype=torch.bfloat16,
+                         device=gout.device).permute(0, 3, 1, 2)
+        gb = torch.empty(COUT if need_b else 0, dtype=torch.bfloat16,
+                         device=gout.device)
+        hip_ext().conv3x3c4_u8_wrw(frames, gout, gw, gb)
+        return None, gw if need_w else None, gb if need_b else None
+
+
+def fused_stem_conv3x3_u8(frames_u8, weight, bias):
+    """The torso's first conv on uint8 (N, 4, H, W) frames: x/255 rounded to
+    bf16, 3x3 stride-1 pad-1 + bias. Device frames must be contiguous at a
+    geometry stem_conv_u8_supported() covers, the weight bf16 channels_last;
+    CPU tensors take the eager reference."""
+    if _use_hip(frames_u8):
+        return _FusedStemConvU8Fn.apply(frames_u8, weight, bias)
+    return torch_ref.stem_conv3x3_u8(frames_u8, weight, bias)
+
+
 def maxpool3x3s2_supported(H, W, C) -> bool:
     ext = hip_ext(required=False)
     return ext is not None and bool(ext.maxpool3x3s2_supported(H, W, C))

@@ -24,6 +24,9 @@
 
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <map>
+#include <mutex>
+#include <string>
 #include <tuple>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
@@ -1812,6 +1815,260 @@ const StemHwLaunch* find_stem_hw(int64_t C, int64_t COUT) {
 }
 
 // ===========================================================================
+// Stem conv from uint8 CHW frames (K2e): the same 3x3 stride-1 pad-1
+// C=4 -> 16 conv, forward and weight/bias gradient, fed with the replay's
+// uint8 (N, 4, H, W) frames as they are; run-time H, W. One pixel's four
+// channels lie H*W bytes apart, so a tap cannot be an 8-byte global load:
+// both kernels first stage an input ROW BAND in LDS, dequantised on the way
+// in, and read every tap from there.
+//   * band: image n, output rows p0 .. p0+BR-1, all W columns. Staged are
+//     input rows p0-1 .. p0+BR and columns -1 .. W as bf16
+//     [BR+2][RS = W+2][4] plus one tail pixel; a thread stages one pixel
+//     (four plane-strided byte loads, contiguous along w over a wave, one
+//     8-byte LDS store). Halo pixels outside the image are zeros and their
+//     address is never formed into a load, so after the barrier padding
+//     needs no predicate. A staged value is
+//     v * (1/255) in fp32 rounded to nearest even:
+//     dequant_u8_bf16_nhwc_c4_kernel's bits.
+//   * forward: K2d's GEMM view (padded K [kh 4][kw 4][c 4], two 16x16x32
+//     chunks, weights as A staged [cout][96] with zero pad slots, the two
+//     weight fragments kept per wave). A lane group's two taps (kh, kw),
+//     (kh, kw+1) of a pixel are 16 contiguous bytes of the band (two 8-byte
+//     reads: a pixel is 8-byte aligned only). The pad slots meet zero
+//     weights, so any finite band value may stand there: slot kw = 3 is the
+//     pixel right of the halo (the next band row's first pixel, or the tail
+//     pixel behind the last row) and row kh = 3 is read as row kh = 0, so
+//     no read leaves the band. The 16 rows of a fragment are the band's
+//     pixels in (p, q) order; fragments straddle band rows and the last one
+//     is ragged. Epilogue in f32: + bias, one rounding, 8-byte stores.
+//   * weight gradient: K2d's method (32-sample chunks, tr16 fragments, fp32
+//     MFMA accumulate over the block's bands, one dense (16, 36) fp32 plane
+//     per m-block, wrw_reduce_kernel's ordered fold; no float atomics). A
+//     pass is one band; block mb takes bands mb, mb + mblocks, ... The
+//     band's gout rows are contiguous; they go through a double-buffered
+//     [128][24] tile (four chunks per barrier). NO im2col tile is built: a
+//     ds_read_tr16_b64 lane supplies its own 8-byte address, so lane r of
+//     group g addresses tap (kh = wave, kw = r & 3) of sample
+//     g*8 + (r>>2) (+4 for the second read) straight in the band. Wave
+//     w < 3 owns kh = w; columns 12..15 (kw = 3) are not stored.
+//   * bias gradient from the same MFMAs: in wave 0 the lanes of column 12
+//     hold 1.0 instead of what they read, so accumulator column 12 is the
+//     block's sum of gout; it goes to b_part[mb][cout] and the bias branch
+//     of wrw_reduce_block folds it with b_planes = mblocks. Samples past the
+//     band's end carry zero gout (their x address is clamped into the band).
+// Both kernels and the staging are compiled without packed fp32
+// instructions.
+// ===========================================================================
+
+#define DRL_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+struct StemU8 {
+  static constexpr int C = 4, COUT = 16, K = 36;
+  static constexpr int THREADS = 256, WAVES = 4;
+  static constexpr int W_BYTES = StemGeom::LDS_BYTES;  // weights + bias
+  static constexpr int GROWS = 128;                    // gout rows per barrier
+  static constexpr int GSTRIDE = COUT + kPadM;         // 24
+  static constexpr int G_BYTES = 2 * GROWS * GSTRIDE * 2;
+  static constexpr int BAND_BUDGET = 32 * 1024;
+  static_assert(W_BYTES % 16 == 0 && G_BYTES % 16 == 0, "band stays aligned");
+  // bytes of a band of br rows at row stride rs pixels, tail pixel included
+  static constexpr int64_t band_bytes(int64_t br, int64_t rs) {
+    return (((br + 2) * rs + 1) * C * 2 + 15) / 16 * 16;
+  }
+};
+
+// Stage rows p0-1 .. p0+BR, columns -1 .. W of image `img` (4, H, W) uint8
+// and the tail pixel: every pixel of the band is written, zeros outside.
+DRL_NO_PK_F32 __device__ __forceinline__ void stem_u8_stage_band(
+    const uint8_t* __restrict__ img, __bf16* band, int H, int W, int p0,
+    int BR, int tid) {
+  const int RS = W + 2;
+  const int npx = (BR + 2) * RS;
+  const int64_t plane = (int64_t)H * W;
+  for (int s = tid; s <= npx; s += StemU8::THREADS) {
+    const int br = s / RS;
+    const int p = p0 - 1 + br;
+    const int q = s - br * RS - 1;
+    s16x4 v = {};
+    if (s < npx && (unsigned)p < (unsigned)H && (unsigned)q < (unsigned)W) {
+      const uint8_t* src = img + (int64_t)p * W + q;
+#pragma unroll
+      for (int c = 0; c < StemU8::C; ++c)
+        v[c] = __builtin_bit_cast(
+            short, __float2bfloat16((float)src[c * plane] * (1.0f / 255.0f)));
+    }
+    *reinterpret_cast<s16x4*>(band + (int64_t)s * StemU8::C) = v;
+  }
+}
+
+__global__ __launch_bounds__(StemU8::THREADS) DRL_NO_PK_F32
+void conv3x3c4_u8_fwd_kernel(
+    const uint8_t* __restrict__ x,      // (N,4,H,W) contiguous
+    const __bf16* __restrict__ weight,  // (16, 36) = (cout, kh, kw, c)
+    const __bf16* __restrict__ bias,    // (16), may be null
+    __bf16* __restrict__ out,           // (N,H,W,16)
+    int H, int W, int BR, int bands) {  // bands per image
+  using G = StemGeom;
+  constexpr int C = G::C, COUT = G::COUT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* wlds = reinterpret_cast<__bf16*>(smem);
+  __bf16* blds = wlds + G::LDS_ELEMS;
+  __bf16* band = reinterpret_cast<__bf16*>(smem + StemU8::W_BYTES);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int n = blockIdx.x / bands;
+  const int p0 = (blockIdx.x - n * bands) * BR;
+  const int RS = W + 2;
+
+  // ---- weights [cout][kh 4][kw 4][c], pad slots zero; bias; the band ----
+  for (int s = tid; s < COUT * 16; s += StemU8::THREADS) {
+    const int co = s >> 4;
+    const int slot = s & 15;
+    const int kh = slot >> 2, kw = slot & 3;
+    s16x4 v = {};
+    if (kh < 3 && kw < 3)
+      v = *reinterpret_cast<const s16x4*>(weight + co * G::K +
+                                          (kh * 3 + kw) * C);
+    *reinterpret_cast<s16x4*>(wlds + co * G::LDS_ROW + slot * C) = v;
+  }
+  if (tid < COUT) blds[tid] = bias ? bias[tid] : (__bf16)0.0f;
+  stem_u8_stage_band(x + (int64_t)n * C * H * W, band, H, W, p0, BR, tid);
+  __syncthreads();
+
+  const int rows = min(BR, H - p0);
+  const int npix = rows * W;
+  const int nfrag = (npix + 15) >> 4;
+  const int g = lane >> 4;
+
+  bf16x8 wa[G::KCHUNKS];
+#pragma unroll
+  for (int kc = 0; kc < G::KCHUNKS; ++kc)
+    wa[kc] = *reinterpret_cast<const bf16x8*>(
+        wlds + (lane & 15) * G::LDS_ROW + kc * 32 + g * 8);
+  const bf16x4 bv = *reinterpret_cast<const bf16x4*>(blds + g * 4);
+  __bf16* oband = out + ((int64_t)n * H + p0) * W * COUT;
+
+  // acc[r] = out[pixel j of the band][g*4 + r]
+#pragma unroll 2
+  for (int f = wave; f < nfrag; f += StemU8::WAVES) {
+    const int j = f * 16 + (lane & 15);
+    const bool ok = j < npix;
+    const int jc = ok ? j : npix - 1;  // ragged tail: decode a real pixel
+    const int pr = jc / W;
+    const int q = jc - pr * W;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kc = 0; kc < G::KCHUNKS; ++kc) {
+      const int kh = 2 * kc + (g >> 1);
+      const int khe = kh < 3 ? kh : 0;  // pad row: any finite row will do
+      const __bf16* t = band + ((pr + khe) * RS + q + 2 * (g & 1)) * C;
+      const s16x4 lo = *reinterpret_cast<const s16x4*>(t);
+      const s16x4 hi = *reinterpret_cast<const s16x4*>(t + C);
+      const s16x8 s = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          wa[kc], __builtin_bit_cast(bf16x8, s), acc, 0, 0, 0);
+    }
+    if (!ok) continue;
+    bf16x4 ov;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ov[r] = (__bf16)(acc[r] + (float)bv[r]);
+    *reinterpret_cast<bf16x4*>(oband + (int64_t)j * COUT + g * 4) = ov;
+  }
+}
+
+__global__ __launch_bounds__(StemU8::THREADS) DRL_NO_PK_F32
+void conv3x3c4_u8_wrw_kernel(
+    const uint8_t* __restrict__ x,    // (N,4,H,W) contiguous
+    const __bf16* __restrict__ gout,  // (N,H,W,16) NHWC grad
+    float* __restrict__ gw_part,      // (mblocks, 576 + kPlanePad) fp32
+    float* __restrict__ b_part,       // (mblocks, 16) fp32, or null
+    int H, int W, int BR, int bands, int n_pass, int mblocks) {
+  using U = StemU8;
+  constexpr int C = U::C, COUT = U::COUT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* g_t = reinterpret_cast<__bf16*>(smem);  // [2][GROWS][GSTRIDE]
+  __bf16* band = reinterpret_cast<__bf16*>(smem + U::G_BYTES);
+
+  const int mb = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  // wave-uniform in an SGPR: the guard below must stay a scalar branch
+  // (tr16 reads need the whole wave active)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, r = lane & 15;
+  const int RS = W + 2;
+  const int grow = tid >> 1, gpiece = tid & 1;  // this thread's gout piece
+
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  int buf = 0;
+  for (int pass = mb; pass < n_pass; pass += mblocks) {
+    const int n = pass / bands;
+    const int p0 = (pass - n * bands) * BR;
+    const int npix = min(BR, H - p0) * W;
+    const int nsub = (npix + U::GROWS - 1) / U::GROWS;
+    const __bf16* gband = gout + ((int64_t)n * H + p0) * W * COUT + gpiece * 8;
+    __syncthreads();  // the previous band is read to its end
+    stem_u8_stage_band(x + (int64_t)n * C * H * W, band, H, W, p0, BR, tid);
+    s16x8 gr = {};
+    if (grow < npix)
+      gr = *reinterpret_cast<const s16x8*>(gband + (int64_t)grow * COUT);
+    for (int sp = 0; sp < nsub; ++sp) {
+      __bf16* gt = g_t + buf * (U::GROWS * U::GSTRIDE);
+      *reinterpret_cast<s16x8*>(gt + grow * U::GSTRIDE + gpiece * 8) = gr;
+      __syncthreads();
+      const int jn = (sp + 1) * U::GROWS + grow;
+      gr = s16x8{};
+      if (jn < npix)
+        gr = *reinterpret_cast<const s16x8*>(gband + (int64_t)jn * COUT);
+      if (wave < 3) {
+#pragma unroll
+        for (int s = 0; s < U::GROWS / 32; ++s) {
+          const bf16x8 gf =
+              tr_frag<U::GSTRIDE>(gt + s * 32 * U::GSTRIDE, lane, 0);
+          // the lane's two samples, clamped into the band (gout is zero
+          // past its end), and its tap (kh = wave, kw = r & 3)
+          const int ja = min(sp * U::GROWS + s * 32 + g * 8 + (r >> 2),
+                             npix - 1);
+          const int jb = min(ja + 4, npix - 1);
+          const int pa = ja / W, pb = jb / W;
+          const __bf16* ta =
+              band + ((pa + wave) * RS + (ja - pa * W) + (r & 3)) * C;
+          const __bf16* tb =
+              band + ((pb + wave) * RS + (jb - pb * W) + (r & 3)) * C;
+          v4bf_w lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+              (__attribute__((address_space(3))) v4bf_w*)ta);
+          v4bf_w hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+              (__attribute__((address_space(3))) v4bf_w*)tb);
+          bf16x8 xf;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { xf[e] = lo[e]; xf[e + 4] = hi[e]; }
+          if (wave == 0 && r == 12) {  // the ones column: bias gradient
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xf[e] = (__bf16)1.0f;
+          }
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf, xf, acc, 0, 0, 0);
+        }
+      }
+      buf ^= 1;
+    }
+  }
+
+  // ---- epilogue: dense (16, 36) plane and the bias partial of this block
+  float* plane = gw_part + (int64_t)mb * (COUT * U::K + kPlanePad);
+  if (wave < 3 && r < 12) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      plane[(g * 4 + e) * U::K + wave * 12 + r] = acc[e];
+  }
+  if (b_part && wave == 0 && r == 12) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b_part[mb * COUT + g * 4 + e] = acc[e];
+  }
+}
+
+// ===========================================================================
 // Max-pool 3x3 stride 2 pad 1 (dilation 1, floor mode) of the torso, NHWC
 // bf16, forward and backward. H, W and C are run-time values, C % 16 == 0;
 // P = (H-1)/2 + 1, Q = (W-1)/2 + 1. Both kernels stream: one lane owns 16
@@ -3134,6 +3391,206 @@ void conv3x3c4_wrw_hw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
   stem_wrw(x, gout, gw, gb, false, "conv3x3c4_wrw_hw");
 }
 
+namespace {
+// Band rows of the uint8 stem kernels where the LDS budget leaves the choice
+// open, the measured best of 6, 8 and 12 at 84x84 for each kernel
+// (profiles/r11_stem_u8.md): the forward wants long bands (fewer halo rows
+// and weight stagings), the weight gradient short ones (more resident
+// blocks to hide a band's staging behind other blocks' MFMAs).
+constexpr int kStemU8FwdBandRows = 12;
+constexpr int kStemU8WrwBandRows = 6;
+
+// The band of a uint8 stem call: BR rows (the wanted count, at most H, at
+// most what StemU8::BAND_BUDGET holds at this W), bands per image, LDS bytes
+// of the two kernels. ok is false where even a three-row band (BR = 1) does
+// not fit. Both launches and the `supported` query take it from here.
+struct StemU8Plan {
+  bool ok;
+  int br, bands, fwd_lds, wrw_lds;
+};
+
+StemU8Plan plan_stem_u8(int64_t H, int64_t W, int64_t band_rows, bool wrw) {
+  StemU8Plan p{};
+  if (H < 1 || W < 1 || StemU8::band_bytes(1, W + 2) > StemU8::BAND_BUDGET)
+    return p;
+  int64_t br = band_rows > 0 ? band_rows
+               : wrw         ? kStemU8WrwBandRows
+                             : kStemU8FwdBandRows;
+  if (br > H) br = H;
+  while (StemU8::band_bytes(br, W + 2) > StemU8::BAND_BUDGET) --br;
+  p.ok = true;
+  p.br = (int)br;
+  p.bands = (int)((H + br - 1) / br);
+  const int band = (int)StemU8::band_bytes(br, W + 2);
+  p.fwd_lds = StemU8::W_BYTES + band;
+  p.wrw_lds = StemU8::G_BYTES + band;
+  return p;
+}
+
+// resident blocks of conv3x3c4_u8_wrw_kernel at this LDS size on the current
+// device: resident_blocks()'s query, kept per (device, LDS bytes)
+int stem_u8_resident(int lds_bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, int>, int> cache;
+  const int dev = at::cuda::current_device();
+  std::lock_guard<std::mutex> lock(mu);
+  int& r = cache[{dev, lds_bytes}];
+  if (r == 0) {
+    int per_cu = 0;
+    TORCH_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &per_cu, (const void*)conv3x3c4_u8_wrw_kernel,
+                    StemU8::THREADS, lds_bytes) == hipSuccess && per_cu > 0,
+                "conv3x3c4_u8_wrw: occupancy query failed");
+    r = per_cu * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  }
+  return r;
+}
+
+// frames (N, 4, H, W) uint8, plain contiguous; returns the call's band plan
+StemU8Plan check_frames_u8(const torch::Tensor& x, int64_t COUT,
+                           int64_t band_rows, bool wrw, const std::string& xn,
+                           const std::string& cout_name) {
+  TORCH_CHECK(x.defined() && x.dim() == 4, xn, " must be 4-D (N, 4, H, W)");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const StemU8Plan p = plan_stem_u8(H, W, band_rows, wrw);
+  TORCH_CHECK(C == StemU8::C && p.ok, xn,
+              ": no uint8 stem conv kernel for this geometry: ", H, "x", W,
+              "x", C);
+  TORCH_CHECK(COUT == StemU8::COUT, cout_name,
+              ": no uint8 stem conv kernel for this geometry: ", H, "x", W,
+              "x", C, " -> ", COUT);
+  check_rows(x, torch::kUInt8, {N, C, H, W}, xn.c_str());
+  // pixels and bands are numbered with int
+  checked_rows(N * H * W + StemU8::GROWS, xn.c_str());
+  return p;
+}
+}  // namespace
+
+bool conv3x3c4_u8_supported(int64_t H, int64_t W, int64_t C, int64_t COUT) {
+  return C == StemU8::C && COUT == StemU8::COUT &&
+         plan_stem_u8(H, W, 0, false).ok;
+}
+
+// x: (N,4,H,W) uint8 contiguous (the replay's frames); weight: (16,4,3,3)
+// logical channels_last bf16; bias: (16) bf16 or empty; out: (N,16,H,W)
+// logical channels_last bf16. One launch on the current stream, no
+// allocation, no sync. band_rows: 0 takes the plan's, > 0 asks for that
+// many (tuning; still cut to H and the LDS budget).
+void conv3x3c4_u8_fwd(torch::Tensor x, torch::Tensor weight,
+                      torch::Tensor bias, torch::Tensor out,
+                      int64_t band_rows) {
+  const std::string who = "conv3x3c4_u8_fwd";
+  const std::string xn = who + " x", wn = who + " weight", on = who + " out",
+                    bn = who + " bias";
+  TORCH_CHECK(weight.defined() && weight.dim() == 4, wn, " must be 4-D");
+  const int64_t COUT = weight.size(0);
+  const StemU8Plan p = check_frames_u8(x, COUT, band_rows, false, xn, wn);
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  check_nhwc(weight, kBF16, COUT, C, 3, 3, wn.c_str());
+  check_nhwc(out, kBF16, N, COUT, H, W, on.c_str());
+  // 8-byte pieces of weight and out
+  TORCH_CHECK((uintptr_t)weight.data_ptr() % 8 == 0, wn, " is misaligned");
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 8 == 0, on, " is misaligned");
+  const __bf16* bias_ptr = opt_vec(bias, COUT, bn.c_str());
+  const int blocks = checked_rows(N * p.bands, xn.c_str());
+  if (blocks == 0) return;
+  hipLaunchKernelGGL(conv3x3c4_u8_fwd_kernel, dim3(blocks),
+                     dim3(StemU8::THREADS), p.fwd_lds, cur_stream(),
+                     (const uint8_t*)x.data_ptr(),
+                     (const __bf16*)weight.data_ptr(), bias_ptr,
+                     (__bf16*)out.data_ptr(), (int)H, (int)W, p.br, p.bands);
+}
+
+namespace {
+// passes (bands), m-grid and residency of a uint8 stem weight gradient:
+// wrw_m_grid's three rules with this kernel's own residency figure
+struct StemU8WrwPlan {
+  int n_pass, resident, mb;
+};
+
+StemU8WrwPlan plan_stem_u8_wrw(const StemU8Plan& p, int64_t N,
+                               const char* who) {
+  StemU8WrwPlan w{};
+  w.n_pass = checked_rows(N * p.bands, who);
+  w.resident = stem_u8_resident(p.wrw_lds);
+  w.mb = wrw_m_grid(w.n_pass, (StemU8::COUT * StemU8::K + kPlanePad) * 4,
+                    w.resident);
+  return w;
+}
+}  // namespace
+
+// x: (N,4,H,W) uint8 contiguous; gout: (N,16,H,W) logical channels_last
+// bf16; gw: (16, 36) fp32 workspace, or the bf16 gradient itself dense in
+// (cout, kh, kw, c) order; gb: (16) of gw's dtype, or empty: then no bias
+// partial is written or folded. Two launches (the kernel and the ordered
+// fold); the only allocations are the partial planes and bias partials.
+void conv3x3c4_u8_wrw(torch::Tensor x, torch::Tensor gout, torch::Tensor gw,
+                      torch::Tensor gb, int64_t band_rows) {
+  const std::string who = "conv3x3c4_u8_wrw";
+  const std::string xn = who + " x", gn = who + " gout", gwn = who + " gw",
+                    gbn = who + " gb";
+  TORCH_CHECK(gout.defined() && gout.dim() == 4, gn, " must be 4-D");
+  const int64_t COUT = gout.size(1);
+  const StemU8Plan p = check_frames_u8(x, COUT, band_rows, true, xn, gn);
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  check_nhwc(gout, kBF16, N, COUT, H, W, (gn + " (x's batch)").c_str());
+  // 16-byte pieces of gout, 16-byte stores to gw
+  TORCH_CHECK((uintptr_t)gout.data_ptr() % 16 == 0, gn, " is misaligned");
+  TORCH_CHECK(gw.defined(), gwn, " is undefined");
+  const bool bf16_out = gw.scalar_type() == kBF16;
+  check_dev(gw, bf16_out ? kBF16 : torch::kFloat32, gwn.c_str());
+  TORCH_CHECK(gw.is_contiguous() ||
+                  (gw.dim() == 4 &&
+                   gw.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              gwn, " must be dense in (cout, kh, kw, c) order");
+  const int64_t n_elem = COUT * 9 * C;
+  TORCH_CHECK(gw.numel() == n_elem, gwn, " must hold ", n_elem,
+              " elements, got ", gw.numel());
+  TORCH_CHECK((uintptr_t)gw.data_ptr() % 16 == 0, gwn, " is misaligned");
+  const bool bias = gb.defined() && gb.numel() > 0;
+  if (bias) check_rows(gb, gw.scalar_type(), {COUT}, gbn.c_str());
+  const StemU8WrwPlan w = plan_stem_u8_wrw(p, N, xn.c_str());
+  const auto f32 = gw.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)w.mb, n_elem + kPlanePad}, f32);
+  torch::Tensor b_part;
+  if (bias) b_part = torch::empty({(int64_t)w.mb, COUT}, f32);
+  float* b_part_ptr = bias ? b_part.data_ptr<float>() : nullptr;
+  auto st = cur_stream();
+  hipLaunchKernelGGL(conv3x3c4_u8_wrw_kernel, dim3(w.mb),
+                     dim3(StemU8::THREADS), p.wrw_lds, st,
+                     (const uint8_t*)x.data_ptr(),
+                     (const __bf16*)gout.data_ptr(), part.data_ptr<float>(),
+                     b_part_ptr, (int)H, (int)W, p.br, p.bands, w.n_pass,
+                     w.mb);
+  // the ordered fold; the bias block folds this kernel's w.mb partials
+  const dim3 fold((unsigned)((n_elem + 63) / 64 + (bias ? 1 : 0)));
+  if (bf16_out)
+    hipLaunchKernelGGL(wrw_reduce_kernel<__bf16>, fold, dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), w.mb,
+                       (int)n_elem, (__bf16*)gw.data_ptr(),
+                       (const float*)b_part_ptr, w.mb, (int)COUT,
+                       bias ? (__bf16*)gb.data_ptr() : nullptr);
+  else
+    hipLaunchKernelGGL(wrw_reduce_kernel<float>, fold, dim3(256), 0, st,
+                       (const float*)part.data_ptr<float>(), w.mb,
+                       (int)n_elem, gw.data_ptr<float>(),
+                       (const float*)b_part_ptr, w.mb, (int)COUT,
+                       bias ? gb.data_ptr<float>() : nullptr);
+}
+
+// (band rows of the forward, band rows of the weight gradient, its m-blocks,
+// its resident blocks) of the uint8 stem kernels on N images of HxW
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv3x3c4_u8_plan(int64_t N,
+                                                                 int64_t H,
+                                                                 int64_t W) {
+  const StemU8Plan f = plan_stem_u8(H, W, 0, false);
+  const StemU8Plan p = plan_stem_u8(H, W, 0, true);
+  TORCH_CHECK(f.ok && p.ok && N >= 0, "conv3x3c4_u8_plan: no uint8 stem conv "
+              "kernel for this geometry: ", H, "x", W);
+  const StemU8WrwPlan w = plan_stem_u8_wrw(p, N, "conv3x3c4_u8_plan");
+  return {f.br, p.br, w.mb, w.resident};
+}
+
 bool maxpool3x3s2_supported(int64_t H, int64_t W, int64_t C) {
   return H >= 1 && W >= 1 && C >= 16 && C % 16 == 0;
 }
@@ -3257,6 +3714,22 @@ void register_conv(pybind11::module_& m) {
   m.def("conv3x3c4_wrw_hw", &conv3x3c4_wrw_hw,
         "conv3x3c4_wrw at any H, W >= 1: the run-time H, W stem kernel");
   m.def("conv3x3c4_hw_supported", &conv3x3c4_hw_supported);
+  m.def("conv3x3c4_u8_fwd", &conv3x3c4_u8_fwd,
+        "stem conv fwd straight from uint8 (N,4,H,W) frames: LDS row band, "
+        "dequant on the way in, NHWC bf16 out (+bias)",
+        py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("out"),
+        py::arg("band_rows") = 0);
+  m.def("conv3x3c4_u8_wrw", &conv3x3c4_u8_wrw,
+        "stem-conv weight and bias grad from uint8 frames, ordered planes, "
+        "bias sum from the same MFMAs; gw/gb are fp32 workspaces or bf16 "
+        "grads",
+        py::arg("x"), py::arg("gout"), py::arg("gw"), py::arg("gb"),
+        py::arg("band_rows") = 0);
+  m.def("conv3x3c4_u8_supported", &conv3x3c4_u8_supported);
+  m.def("conv3x3c4_u8_plan", &conv3x3c4_u8_plan,
+        "(forward band rows, weight-grad band rows, m-blocks, resident "
+        "blocks) of the uint8 stem kernels",
+        py::arg("N"), py::arg("H"), py::arg("W"));
   m.def("conv3x3p1_wrw_plan", &conv3x3p1_wrw_plan,
         "(m-blocks, rows per pass, resident blocks) of a conv3x3p1_wrw call",
         py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"),

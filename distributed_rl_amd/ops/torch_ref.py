@@ -40,6 +40,34 @@ def conv3x3_res(x, weight, bias=None, relu_in: bool = False,
 
 
 # ---------------------------------------------------------------------------
+# K2e — the torso's first conv on uint8 (N, 4, H, W) frames: x/255 rounded
+#       to bf16 (the bits ops.dequant_frames_nhwc writes), then the plain
+#       conv in the dtype of the weight / of gout (fp64 in the tests)
+# ---------------------------------------------------------------------------
+
+
+def _stem_u8_dequant(frames: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    return (frames.float() / 255).bfloat16().to(dtype)
+
+
+def stem_conv3x3_u8(frames, weight, bias=None) -> torch.Tensor:
+    return torch.nn.functional.conv2d(
+        _stem_u8_dequant(frames, weight.dtype), weight, bias, padding=1)
+
+
+def stem_conv3x3_u8_grads(frames, gout) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(gw (COUT, 36) in (kh, kw, c) order, gb (COUT)) of that conv for the
+    output gradient gout (N, COUT, H, W)."""
+    cout, c = gout.shape[1], frames.shape[1]
+    w = torch.zeros(cout, c, 3, 3, dtype=gout.dtype, requires_grad=True)
+    b = torch.zeros(cout, dtype=gout.dtype, requires_grad=True)
+    y = torch.nn.functional.conv2d(
+        _stem_u8_dequant(frames, gout.dtype), w, b, padding=1)
+    gw, gb = torch.autograd.grad(y, [w, b], gout)
+    return gw.permute(0, 2, 3, 1).reshape(cout, 9 * c), gb
+
+
+# ---------------------------------------------------------------------------
 # K2c — max-pool 3x3 stride 2 pad 1 of the IMPALA-ResNet torso
 #       (models/base_agent.py ImpalaResNet: nn.MaxPool2d(3, 2, 1)); the
 #       winning tap kh*3 + kw per output element, and the input gradient as
