@@ -937,14 +937,30 @@ def dueling_nstep_dqn_loss(adv_s, val_s, adv_on, val_on, adv_tg, val_tg,
 # ---------------------------------------------------------------------------
 # K3+K4+heads fused (round 2b): the dueling head projections join the loss
 # kernel; backward is closed-form dh + one reduction kernel for the head
-# weight/bias grads. Geometry-locked to hidden=512/A=6 (the shipped cfg).
+# weight/bias grads. hidden=512; A=6 (the shipped cfg) runs the compile-time
+# kernels, any other A in 2..18 the run-time-A MFMA kernels
+# (dueling_q_loss_any_*). DRL_QHEAD_ANY=1 sends A=6 through those too.
 # ---------------------------------------------------------------------------
 
 
 def has_dueling_q_loss(hidden: int, actions: int) -> bool:
     ext = hip_ext(required=False)
-    return (ext is not None and hasattr(ext, "dueling_q_loss_fwd")
-            and hidden == 512 and actions == 6)
+    if ext is None or not hasattr(ext, "dueling_q_loss_fwd"):
+        return False
+    if hidden == 512 and actions == 6:
+        return True
+    return (hasattr(ext, "dueling_q_loss_any_fwd")
+            and ext.dueling_q_loss_any_supported(hidden, actions))
+
+
+def _qhead_any(actions: int) -> bool:
+    # read per call: the A = 6 default stays on the compile-time kernels
+    return actions != 6 or os.environ.get("DRL_QHEAD_ANY", "0") == "1"
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    return t if t.data_ptr() % 16 == 0 else t.clone(
+        memory_format=torch.contiguous_format)
 
 
 class _DuelingQLossFn(torch.autograd.Function):
@@ -958,7 +974,14 @@ class _DuelingQLossFn(torch.autograd.Function):
         acc2 = torch.zeros(2, dtype=torch.float32, device=dev)
         prio = torch.empty(B, dtype=torch.float32, device=dev)
         coef = torch.empty(B, dtype=torch.float32, device=dev)
-        ext.dueling_q_loss_fwd(
+        any_a = _qhead_any(wa.shape[0])
+        fwd = ext.dueling_q_loss_any_fwd if any_a else ext.dueling_q_loss_fwd
+        if any_a:
+            # the any-A kernels read the heads 16 bytes at a time; a head
+            # that is a view into a flat parameter buffer can sit at any
+            # 2-byte offset (the A-element bias before it), so it is staged
+            wa, wv, wa_t, wv_t = (_aligned16(t) for t in (wa, wv, wa_t, wv_t))
+        fwd(
             h_s.contiguous(), h_on.contiguous(), h_tg.contiguous(),
             wa.contiguous(), ba.contiguous(), wv.reshape(-1).contiguous(),
             bv.contiguous(), wa_t.contiguous(), ba_t.contiguous(),
@@ -968,6 +991,7 @@ class _DuelingQLossFn(torch.autograd.Function):
             acc2[0:1], prio, coef, acc2[1:2], bool(pre_act),
         )
         ctx.pre_act = bool(pre_act)
+        ctx.any_a = any_a
         ctx.save_for_backward(coef, actions, wa, wv, h_s)
         loss_out, qmean = acc2[0], acc2[1]
         ctx.mark_non_differentiable(prio, qmean)
@@ -980,14 +1004,16 @@ class _DuelingQLossFn(torch.autograd.Function):
         B = h_s.shape[0]
         dev = h_s.device
         dh = torch.empty(B, 1024, dtype=torch.bfloat16, device=dev)
-        dwa = torch.empty(6, 512, dtype=torch.bfloat16, device=dev)
-        dba = torch.empty(6, dtype=torch.bfloat16, device=dev)
+        A = wa.shape[0]
+        dwa = torch.empty(A, 512, dtype=torch.bfloat16, device=dev)
+        dba = torch.empty(A, dtype=torch.bfloat16, device=dev)
         dwv = torch.empty(1, 512, dtype=torch.bfloat16, device=dev)
         dbv = torch.empty(1, dtype=torch.bfloat16, device=dev)
-        ext.dueling_q_loss_bwd(coef, actions, gout.reshape(1).contiguous(),
-                               wa.contiguous(), wv.reshape(-1).contiguous(),
-                               h_s.contiguous(), dh, dwa, dba, dwv, dbv,
-                               ctx.pre_act)
+        bwd = (ext.dueling_q_loss_any_bwd if ctx.any_a
+               else ext.dueling_q_loss_bwd)
+        bwd(coef, actions, gout.reshape(1).contiguous(), wa.contiguous(),
+            wv.reshape(-1).contiguous(), h_s.contiguous(), dh, dwa, dba, dwv,
+            dbv, ctx.pre_act)
         return (dh, dwa, dba, dwv, dbv) + (None,) * 13
 
 

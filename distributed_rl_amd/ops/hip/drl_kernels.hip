@@ -909,6 +909,24 @@ void dueling_q_loss_bwd(torch::Tensor grad_coef, torch::Tensor act,
                         torch::Tensor h_s, torch::Tensor dh, torch::Tensor dwa,
                         torch::Tensor dba, torch::Tensor dwv,
                         torch::Tensor dbv, bool pre_act);
+bool dueling_q_loss_any_supported(int64_t hidden, int64_t actions);
+void dueling_q_loss_any_fwd(torch::Tensor h_s, torch::Tensor h_on,
+                            torch::Tensor h_tg, torch::Tensor wa,
+                            torch::Tensor ba, torch::Tensor wv,
+                            torch::Tensor bv, torch::Tensor wa_t,
+                            torch::Tensor ba_t, torch::Tensor wv_t,
+                            torch::Tensor bv_t, torch::Tensor act,
+                            torch::Tensor rew, torch::Tensor done,
+                            torch::Tensor w, double gamma_n, double alpha,
+                            torch::Tensor loss_out, torch::Tensor prio_out,
+                            torch::Tensor grad_coef, torch::Tensor qmax_out,
+                            bool pre_act);
+void dueling_q_loss_any_bwd(torch::Tensor grad_coef, torch::Tensor act,
+                            torch::Tensor gout, torch::Tensor wa,
+                            torch::Tensor wv, torch::Tensor h_s,
+                            torch::Tensor dh, torch::Tensor dwa,
+                            torch::Tensor dba, torch::Tensor dwv,
+                            torch::Tensor dbv, bool pre_act);
 void r2d2_loss_fwd(torch::Tensor q_train, torch::Tensor q_tgt,
                    torch::Tensor act, torch::Tensor rew, torch::Tensor done,
                    torch::Tensor w, int64_t m, int64_t n_step, double gamma,
@@ -990,6 +1008,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "heads+dueling+n-step-DQN loss in one kernel (K3+K4+heads)");
   m.def("dueling_q_loss_bwd", &dueling_q_loss_bwd,
         "closed-form dh + head weight/bias grads (2 kernels)");
+  m.def("dueling_q_loss_any_supported", &dueling_q_loss_any_supported,
+        "hidden 512 and 2..18 actions");
+  m.def("dueling_q_loss_any_fwd", &dueling_q_loss_any_fwd,
+        "heads+dueling+n-step-DQN loss at any action count 2..18: bf16-MFMA "
+        "heads, ordered loss fold");
+  m.def("dueling_q_loss_any_bwd", &dueling_q_loss_any_bwd,
+        "any-A closed-form dh + fp32-MFMA head weight/bias grads");
   m.def("r2d2_loss_fwd", &r2d2_loss_fwd,
         "R2D2 n-step targets + rescale + IS loss, one kernel (K4/K6 seq)");
   m.def("r2d2_prio", &r2d2_prio, "eta-mix sequence priority (K7)");
@@ -2948,6 +2973,506 @@ void dueling_q_loss_bwd(torch::Tensor grad_coef, torch::Tensor act,
                      dim3(ceil_div(7 * 513, kBlock)), dim3(kBlock), 0,
                      cur_stream(), ws.data_ptr<float>(),
                      (__bf16*)dwa.data_ptr(), (__bf16*)dba.data_ptr(),
+                     (__bf16*)dwv.data_ptr(), (__bf16*)dbv.data_ptr());
+}
+
+// ===========================================================================
+// K3+K4+heads at any action count: A is a kernel argument, 2 <= A <= 18,
+// hidden stays 512 per stream. Same formulas as the (512, 6) family above;
+// what changes is how the work is split.
+//   fwd: the heads are a GEMM, q[16 rows][16 heads] = h[16][512] @ W^T on
+//        v_mfma_f32_16x16x32_bf16. A block takes 16 batch rows; its four
+//        waves split K (128 k each), so every head element is read by
+//        exactly one wave of the block — the head fragments come straight
+//        from L2, an LDS stage would add a round trip and no reuse. Tiles:
+//        NB = ceil(A / 16) adv column blocks for each of h_s / h_on (online
+//        heads) and h_tg (target heads), plus one value tile (column 0 live)
+//        for h_s and h_tg: 3 NB + 2 accumulators per wave. The waves'
+//        partial tiles are summed through LDS in wave order, 16 lanes run
+//        the scalar epilogue (one row each), and the block writes one
+//        (loss, qmax) partial summed in row order. A one-wave fold adds the
+//        block partials in block order: no float atomics, so loss and qmean
+//        are bit-identical across calls.
+//   dh:  a thread owns 8 consecutive k, forms the column mean over A once,
+//        then walks its rows with one 16-byte store each.
+//   dW:  dW[j][k] = sum_b alpha[b][j] * h_s[b][k] with alpha in fp32, on
+//        v_mfma_f32_16x16x4_f32 (alpha^T is the A operand, so it is never
+//        rounded). One 16-byte load of h_s per lane feeds eight MFMAs; a
+//        wave covers 128 columns from registers, four batch rows per step.
+//        Grid (head block, b-slice); each slice writes an fp32 plane, the
+//        fold sums the planes in slice order and rounds once to bf16.
+// Fragment maps:
+//   bf16 16x16x32: A lane l = A[row l&15][k 8(l>>4)+j], B lane l =
+//     B[k 8(l>>4)+j][col l&15], D lane l = D[row 4(l>>4)+r][col l&15].
+//   f32 16x16x4:  A lane l = A[row l&15][k l>>4], B lane l = B[k l>>4]
+//     [col l&15], D as above. In dW row = head, k = batch row, and MFMA u
+//     of a step takes element u of the lane's 8-element piece, so tile u,
+//     col n is hidden column kbase + 8n + u: lane l ends up with 8
+//     consecutive columns of 4 heads.
+// ===========================================================================
+namespace {
+
+constexpr int kQaRows = 16;      // batch rows per forward block
+constexpr int kQaDhRows = 8;     // batch rows per dh block
+constexpr int kQaSlices = 32;    // most b-slices of the dW kernel
+
+__device__ __forceinline__ bf16x8_k5 qa_relu8(bf16x8_k5 v) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (!((float)v[j] > 0.0f)) v[j] = (__bf16)0.0f;
+  return v;
+}
+
+template <bool PRE>
+__device__ __forceinline__ bf16x8_k5 qa_load_h(const __bf16* p, bool live) {
+  bf16x8_k5 v = {};
+  if (live) {
+    v = *reinterpret_cast<const bf16x8_k5*>(p);
+    if constexpr (PRE) v = qa_relu8(v);
+  }
+  return v;
+}
+
+__device__ __forceinline__ bf16x8_k5 qa_load_w(const __bf16* p, bool live) {
+  bf16x8_k5 v = {};
+  if (live) v = *reinterpret_cast<const bf16x8_k5*>(p);
+  return v;
+}
+
+// tiles of a wave: [0, NB) q_s, [NB, 2NB) q_on, [2NB, 3NB) q_tg, then the
+// value tiles of h_s and h_tg
+template <bool PRE, int NB>
+__global__ __launch_bounds__(256) void dueling_q_loss_any_fwd_kernel(
+    const __bf16* __restrict__ h_s, const __bf16* __restrict__ h_on,
+    const __bf16* __restrict__ h_tg, const __bf16* __restrict__ wa,
+    const __bf16* __restrict__ ba, const __bf16* __restrict__ wv,
+    const __bf16* __restrict__ bv, const __bf16* __restrict__ wa_t,
+    const __bf16* __restrict__ ba_t, const __bf16* __restrict__ wv_t,
+    const __bf16* __restrict__ bv_t, const int64_t* __restrict__ act,
+    const float* __restrict__ rew, const float* __restrict__ done,
+    const float* __restrict__ w, int B, int A, float gamma_n, float alpha,
+    float* __restrict__ part,  // (blocks, 2)
+    float* __restrict__ prio_out, float* __restrict__ grad_coef) {
+  constexpr int HH = 512;
+  constexpr int NT = 3 * NB + 2;
+  __shared__ float red[4][NT][16][16];
+  __shared__ float rowsum[kQaRows][2];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int l15 = lane & 15;
+  const int kq = (lane >> 4) * 8;
+  const int b0 = blockIdx.x * kQaRows;
+  const int brow = b0 + l15;
+  const bool row_live = brow < B;
+  const int64_t hoff = (int64_t)brow * (2 * HH);
+
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int k = wave * 128 + c * 32 + kq;
+    const bf16x8_k5 a_s = qa_load_h<PRE>(h_s + hoff + k, row_live);
+    const bf16x8_k5 a_on = qa_load_h<PRE>(h_on + hoff + k, row_live);
+    const bf16x8_k5 a_tg = qa_load_h<PRE>(h_tg + hoff + k, row_live);
+    const bf16x8_k5 v_s = qa_load_h<PRE>(h_s + hoff + HH + k, row_live);
+    const bf16x8_k5 v_tg = qa_load_h<PRE>(h_tg + hoff + HH + k, row_live);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const int head = nb * 16 + l15;
+      const bf16x8_k5 wf = qa_load_w(wa + (int64_t)head * HH + k, head < A);
+      const bf16x8_k5 wtf =
+          qa_load_w(wa_t + (int64_t)head * HH + k, head < A);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_s, wf, acc[nb], 0,
+                                                        0, 0);
+      acc[NB + nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          a_on, wf, acc[NB + nb], 0, 0, 0);
+      acc[2 * NB + nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          a_tg, wtf, acc[2 * NB + nb], 0, 0, 0);
+    }
+    const bf16x8_k5 wvf = qa_load_w(wv + k, l15 == 0);
+    const bf16x8_k5 wvtf = qa_load_w(wv_t + k, l15 == 0);
+    acc[3 * NB] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v_s, wvf,
+                                                          acc[3 * NB], 0, 0, 0);
+    acc[3 * NB + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+        v_tg, wvtf, acc[3 * NB + 1], 0, 0, 0);
+  }
+  const int crow = (lane >> 4) * 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][t][crow + r][l15] = acc[t][r];
+  __syncthreads();
+  // wave order 0..3; thread (row, col) owns its element of every tile
+  {
+    const int row = tid >> 4, col = tid & 15;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      float v = red[0][t][row][col];
+      v += red[1][t][row][col];
+      v += red[2][t][row][col];
+      v += red[3][t][row][col];
+      red[0][t][row][col] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < kQaRows) {
+    const int row = tid;
+    const int b = b0 + row;
+    float l_term = 0.f, q_term = 0.f;
+    if (b < B) {
+      float mean_s = 0.f, mean_tg = 0.f, best = -1e30f;
+      float smax = 0.f, q_sa = 0.f;
+      int a_star = 0;
+      const int a_b = (int)act[b];
+      for (int j = 0; j < A; ++j) {
+        const int nb = j >> 4, cj = j & 15;
+        const float bj = (float)ba[j];
+        const float qs = red[0][nb][row][cj] + bj;
+        const float adv_on = red[0][NB + nb][row][cj] + bj;
+        const float qt = red[0][2 * NB + nb][row][cj] + (float)ba_t[j];
+        if (adv_on > best) { best = adv_on; a_star = j; }
+        mean_s += qs;
+        mean_tg += qt;
+        smax = j == 0 ? qs : fmaxf(smax, qs);
+        if (j == a_b) q_sa = qs;
+      }
+      mean_s /= A;
+      mean_tg /= A;
+      const float vs_full = red[0][3 * NB][row][0] + (float)bv[0];
+      const float vt_full = red[0][3 * NB + 1][row][0] + (float)bv_t[0];
+      const float q_tg_star =
+          red[0][2 * NB + (a_star >> 4)][row][a_star & 15] +
+          (float)ba_t[a_star];
+      const float q_tgt = q_tg_star - mean_tg + vt_full;
+      const float target = rew[b] + gamma_n * q_tgt * (1.0f - done[b]);
+      const float q = q_sa - mean_s + vs_full;
+      const float raw = target - q;
+      const float td = fminf(1.0f, fmaxf(-1.0f, raw));
+      prio_out[b] = __powf(fabsf(td) + 1e-7f, alpha);
+      const float in_range = (raw >= -1.0f && raw <= 1.0f) ? 1.0f : 0.0f;
+      const float invB = 1.0f / B;
+      grad_coef[b] = w[b] * td * in_range * invB;
+      l_term = 0.5f * w[b] * td * td * invB;
+      q_term = (smax - mean_s + vs_full) * invB;
+    }
+    rowsum[row][0] = l_term;
+    rowsum[row][1] = q_term;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    float v = 0.f;
+    for (int r = 0; r < kQaRows; ++r)
+      if (b0 + r < B) v += rowsum[r][tid];
+    part[(int64_t)blockIdx.x * 2 + tid] = v;
+  }
+}
+
+// lane 0 folds the loss partials, lane 1 the qmax partials, in block order
+__global__ __launch_bounds__(64) void dueling_q_loss_any_fold_kernel(
+    const float* __restrict__ part, int nblocks, float* __restrict__ loss_out,
+    float* __restrict__ qmax_out) {
+  const int t = threadIdx.x;
+  if (t >= 2) return;
+  float v = 0.f;
+  for (int i = 0; i < nblocks; ++i) v += part[(int64_t)i * 2 + t];
+  (t == 0 ? loss_out : qmax_out)[0] = v;
+}
+
+// block = 2 row lanes x 128 column threads (64 on the adv half, 64 on val)
+template <bool PRE>
+__global__ __launch_bounds__(256) void dueling_q_loss_any_bwd_dh_kernel(
+    const float* __restrict__ grad_coef, const int64_t* __restrict__ act,
+    const float* __restrict__ gout, const __bf16* __restrict__ wa,
+    const __bf16* __restrict__ wv, const __bf16* __restrict__ h_s, int B,
+    int A, __bf16* __restrict__ dh) {
+  constexpr int HH = 512;
+  const int ct = threadIdx.x & 127;
+  const int k = ct * 8;              // column in [0, 1024)
+  const bool adv = k < HH;
+  float m[8];
+  if (adv) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) m[u] = 0.f;
+    for (int j = 0; j < A; ++j) {
+      const bf16x8_k5 r =
+          *reinterpret_cast<const bf16x8_k5*>(wa + (int64_t)j * HH + k);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) m[u] += (float)r[u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) m[u] /= A;
+  } else {
+    const bf16x8_k5 r = *reinterpret_cast<const bf16x8_k5*>(wv + (k - HH));
+#pragma unroll
+    for (int u = 0; u < 8; ++u) m[u] = (float)r[u];
+  }
+  const float g = gout[0];
+  const int b_end = min(B, (int)(blockIdx.x + 1) * kQaDhRows);
+  for (int b = blockIdx.x * kQaDhRows + (threadIdx.x >> 7); b < b_end;
+       b += 2) {
+    const float c = -grad_coef[b] * g;
+    float v[8];
+    if (adv) {
+      const bf16x8_k5 r = *reinterpret_cast<const bf16x8_k5*>(
+          wa + (int64_t)act[b] * HH + k);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = c * ((float)r[u] - m[u]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = c * m[u];
+    }
+    const int64_t off = (int64_t)b * (2 * HH) + k;
+    if constexpr (PRE) {
+      const bf16x8_k5 h = *reinterpret_cast<const bf16x8_k5*>(h_s + off);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (!((float)h[u] > 0.0f)) v[u] = 0.0f;
+    }
+    bf16x8_k5 o;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) o[u] = (__bf16)v[u];
+    *reinterpret_cast<bf16x8_k5*>(dh + off) = o;
+  }
+}
+
+// grid (NB + 1, nsl): head block x < NB is adv heads 16x .. 16x+15 against
+// the adv half, x == NB the value head against the val half. Wave w takes
+// columns 128w .. 128w+127 of that half. Slice s takes the 4-row groups
+// s, s + nsl, ... Planes: ws[nsl][A + 1][512], then wsb[nsl][A + 1].
+template <bool PRE>
+__global__ __launch_bounds__(256) void dueling_q_loss_any_bwd_dw_kernel(
+    const float* __restrict__ grad_coef, const int64_t* __restrict__ act,
+    const float* __restrict__ gout, const __bf16* __restrict__ h_s, int B,
+    int A, float* __restrict__ ws) {
+  constexpr int HH = 512;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int NB = (A + 15) >> 4;
+  const int hb = blockIdx.x;
+  const bool is_val = hb == NB;
+  const int sl = blockIdx.y, nsl = gridDim.y;
+  const int head = hb * 16 + l15;  // this lane's row of alpha^T (adv blocks)
+  const bool head_live = is_val ? l15 == 0 : head < A;
+  const float inv_a = 1.0f / A;
+  const float g = gout[0];
+  const int col = (is_val ? HH : 0) + wave * 128 + l15 * 8;
+
+  f32x4 acc[8], accb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 8; ++u) acc[u] = {0.f, 0.f, 0.f, 0.f};
+  const int ngroups = (B + 3) >> 2;
+  for (int gr = sl; gr < ngroups; gr += nsl) {
+    const int b = gr * 4 + l4;
+    float al = 0.f;
+    bf16x8_k5 h = {};
+    if (b < B) {
+      const float c = -grad_coef[b] * g;
+      if (head_live)
+        al = is_val ? c
+                    : c * (((int)act[b] == head ? 1.0f : 0.0f) - inv_a);
+      h = *reinterpret_cast<const bf16x8_k5*>(h_s + (int64_t)b * (2 * HH) +
+                                              col);
+      if constexpr (PRE) h = qa_relu8(h);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(al, (float)h[u], acc[u],
+                                                    0, 0, 0);
+    if (wave == 0)  // bias gradients: alpha^T against a ones operand
+      accb = __builtin_amdgcn_mfma_f32_16x16x4f32(al, 1.0f, accb, 0, 0, 0);
+  }
+  const int rows = A + 1;
+  float* plane = ws + (int64_t)sl * rows * HH;
+  float* bias = ws + (int64_t)nsl * rows * HH + (int64_t)sl * rows;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int t = l4 * 4 + r;  // row of the accumulator tile
+    int out_row;
+    if (is_val) {
+      if (t != 0) continue;
+      out_row = A;
+    } else {
+      out_row = hb * 16 + t;
+      if (out_row >= A) continue;
+    }
+    float* p = plane + (int64_t)out_row * HH + wave * 128 + l15 * 8;
+    *reinterpret_cast<float4*>(p) =
+        make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
+    *reinterpret_cast<float4*>(p + 4) =
+        make_float4(acc[4][r], acc[5][r], acc[6][r], acc[7][r]);
+    if (wave == 0 && l15 == 0) bias[out_row] = accb[r];
+  }
+}
+
+// element i of [(A + 1) x 512 weights | (A + 1) biases]: planes summed in
+// slice order, rounded once
+__global__ void dueling_q_loss_any_bwd_dw_fold_kernel(
+    const float* __restrict__ ws, int A, int nsl, __bf16* __restrict__ dwa,
+    __bf16* __restrict__ dba, __bf16* __restrict__ dwv,
+    __bf16* __restrict__ dbv) {
+  constexpr int HH = 512;
+  const int rows = A + 1;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * (HH + 1)) return;
+  const bool is_w = i < rows * HH;
+  const int e = is_w ? i : i - rows * HH;
+  const float* src = is_w ? ws + e : ws + (int64_t)nsl * rows * HH + e;
+  const int64_t stride = is_w ? (int64_t)rows * HH : rows;
+  float v = 0.f;
+  for (int s = 0; s < nsl; ++s) v += src[s * stride];
+  if (is_w) {
+    if (e < A * HH)
+      dwa[e] = (__bf16)v;
+    else
+      dwv[e - A * HH] = (__bf16)v;
+  } else {
+    if (e < A)
+      dba[e] = (__bf16)v;
+    else
+      dbv[0] = (__bf16)v;
+  }
+}
+
+void check_align16(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what,
+              " must be 16-byte aligned");
+}
+
+// (A, 512) head matrix with A in 2..18; returns A
+int check_heads(const torch::Tensor& wa, const char* what) {
+  check_shape(wa, torch::kBFloat16, 2, what);
+  TORCH_CHECK(wa.size(1) == 512 && wa.size(0) >= 2 && wa.size(0) <= 18, what,
+              " must be (A, 512) with 2 <= A <= 18, got ", wa.sizes());
+  check_align16(wa, what);
+  return (int)wa.size(0);
+}
+}  // namespace
+
+bool dueling_q_loss_any_supported(int64_t hidden, int64_t actions) {
+  return hidden == 512 && actions >= 2 && actions <= 18;
+}
+
+void dueling_q_loss_any_fwd(torch::Tensor h_s, torch::Tensor h_on,
+                            torch::Tensor h_tg, torch::Tensor wa,
+                            torch::Tensor ba, torch::Tensor wv,
+                            torch::Tensor bv, torch::Tensor wa_t,
+                            torch::Tensor ba_t, torch::Tensor wv_t,
+                            torch::Tensor bv_t, torch::Tensor act,
+                            torch::Tensor rew, torch::Tensor done,
+                            torch::Tensor w, double gamma_n, double alpha,
+                            torch::Tensor loss_out, torch::Tensor prio_out,
+                            torch::Tensor grad_coef, torch::Tensor qmax_out,
+                            bool pre_act) {
+  constexpr auto bf = torch::kBFloat16;
+  check_shape(h_s, bf, 2, "h_s");
+  TORCH_CHECK(h_s.size(1) == 1024, "h_s must be (B, 1024), got ",
+              h_s.sizes());
+  const int64_t nh = checked_count(h_s.numel(), "h_s");
+  check_align16(h_s, "h_s");
+  const int B = (int)h_s.size(0);
+  check_vec(h_on, bf, nh, h_s, "h_on");
+  check_align16(h_on, "h_on");
+  check_vec(h_tg, bf, nh, h_s, "h_tg");
+  check_align16(h_tg, "h_tg");
+  const int A = check_heads(wa, "wa");
+  check_vec(wa, bf, (int64_t)A * 512, h_s, "wa");
+  check_vec(ba, bf, A, h_s, "ba");
+  check_vec(wv, bf, 512, h_s, "wv");
+  check_align16(wv, "wv");
+  check_vec(bv, bf, 1, h_s, "bv");
+  check_vec(wa_t, bf, (int64_t)A * 512, h_s, "wa_t");
+  TORCH_CHECK(wa_t.dim() == 2 && wa_t.size(0) == A, "wa_t must be (", A,
+              ", 512) like wa, got ", wa_t.sizes());
+  check_align16(wa_t, "wa_t");
+  check_vec(ba_t, bf, A, h_s, "ba_t");
+  check_vec(wv_t, bf, 512, h_s, "wv_t");
+  check_align16(wv_t, "wv_t");
+  check_vec(bv_t, bf, 1, h_s, "bv_t");
+  check_vec(act, torch::kInt64, B, h_s, "act");
+  check_vec(rew, torch::kFloat32, B, h_s, "rew");
+  check_vec(done, torch::kFloat32, B, h_s, "done");
+  check_vec(w, torch::kFloat32, B, h_s, "w");
+  check_vec(loss_out, torch::kFloat32, 1, h_s, "loss_out");
+  check_vec(prio_out, torch::kFloat32, B, h_s, "prio_out");
+  check_vec(grad_coef, torch::kFloat32, B, h_s, "grad_coef");
+  check_vec(qmax_out, torch::kFloat32, 1, h_s, "qmax_out");
+  const int nblocks = (B + kQaRows - 1) / kQaRows;
+  auto part = torch::empty({(int64_t)nblocks * 2},
+                           torch::dtype(torch::kFloat32).device(h_s.device()));
+  auto kern = A <= 16 ? (pre_act ? dueling_q_loss_any_fwd_kernel<true, 1>
+                                 : dueling_q_loss_any_fwd_kernel<false, 1>)
+                      : (pre_act ? dueling_q_loss_any_fwd_kernel<true, 2>
+                                 : dueling_q_loss_any_fwd_kernel<false, 2>);
+  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), 0, cur_stream(),
+                     (const __bf16*)h_s.data_ptr(),
+                     (const __bf16*)h_on.data_ptr(),
+                     (const __bf16*)h_tg.data_ptr(),
+                     (const __bf16*)wa.data_ptr(), (const __bf16*)ba.data_ptr(),
+                     (const __bf16*)wv.data_ptr(), (const __bf16*)bv.data_ptr(),
+                     (const __bf16*)wa_t.data_ptr(),
+                     (const __bf16*)ba_t.data_ptr(),
+                     (const __bf16*)wv_t.data_ptr(),
+                     (const __bf16*)bv_t.data_ptr(), act.data_ptr<int64_t>(),
+                     rew.data_ptr<float>(), done.data_ptr<float>(),
+                     w.data_ptr<float>(), B, A, (float)gamma_n, (float)alpha,
+                     part.data_ptr<float>(), prio_out.data_ptr<float>(),
+                     grad_coef.data_ptr<float>());
+  hipLaunchKernelGGL(dueling_q_loss_any_fold_kernel, dim3(1), dim3(64), 0,
+                     cur_stream(), part.data_ptr<float>(), nblocks,
+                     loss_out.data_ptr<float>(), qmax_out.data_ptr<float>());
+}
+
+void dueling_q_loss_any_bwd(torch::Tensor grad_coef, torch::Tensor act,
+                            torch::Tensor gout, torch::Tensor wa,
+                            torch::Tensor wv, torch::Tensor h_s,
+                            torch::Tensor dh, torch::Tensor dwa,
+                            torch::Tensor dba, torch::Tensor dwv,
+                            torch::Tensor dbv, bool pre_act) {
+  constexpr auto bf = torch::kBFloat16;
+  check_shape(h_s, bf, 2, "h_s");
+  TORCH_CHECK(h_s.size(1) == 1024, "h_s must be (B, 1024), got ",
+              h_s.sizes());
+  const int64_t nh = checked_count(h_s.numel(), "h_s");
+  check_align16(h_s, "h_s");
+  const int B = (int)h_s.size(0);
+  check_vec(grad_coef, torch::kFloat32, B, h_s, "grad_coef");
+  check_vec(act, torch::kInt64, B, h_s, "act");
+  check_vec(gout, torch::kFloat32, 1, h_s, "gout");
+  const int A = check_heads(wa, "wa");
+  check_vec(wa, bf, (int64_t)A * 512, h_s, "wa");
+  check_vec(wv, bf, 512, h_s, "wv");
+  check_align16(wv, "wv");
+  check_vec(dh, bf, nh, h_s, "dh");
+  check_align16(dh, "dh");
+  check_vec(dwa, bf, (int64_t)A * 512, h_s, "dwa");
+  check_vec(dba, bf, A, h_s, "dba");
+  check_vec(dwv, bf, 512, h_s, "dwv");
+  check_vec(dbv, bf, 1, h_s, "dbv");
+  const int nsl = std::min(kQaSlices, (B + 3) / 4);
+  auto ws = torch::empty({(int64_t)nsl * (A + 1) * 513},
+                         torch::dtype(torch::kFloat32).device(h_s.device()));
+  hipLaunchKernelGGL((pre_act ? dueling_q_loss_any_bwd_dh_kernel<true>
+                              : dueling_q_loss_any_bwd_dh_kernel<false>),
+                     dim3((B + kQaDhRows - 1) / kQaDhRows), dim3(256), 0,
+                     cur_stream(), grad_coef.data_ptr<float>(),
+                     act.data_ptr<int64_t>(), gout.data_ptr<float>(),
+                     (const __bf16*)wa.data_ptr(), (const __bf16*)wv.data_ptr(),
+                     (const __bf16*)h_s.data_ptr(), B, A,
+                     (__bf16*)dh.data_ptr());
+  hipLaunchKernelGGL((pre_act ? dueling_q_loss_any_bwd_dw_kernel<true>
+                              : dueling_q_loss_any_bwd_dw_kernel<false>),
+                     dim3((A + 15) / 16 + 1, nsl), dim3(256), 0, cur_stream(),
+                     grad_coef.data_ptr<float>(), act.data_ptr<int64_t>(),
+                     gout.data_ptr<float>(), (const __bf16*)h_s.data_ptr(), B,
+                     A, ws.data_ptr<float>());
+  hipLaunchKernelGGL(dueling_q_loss_any_bwd_dw_fold_kernel,
+                     dim3(ceil_div((int64_t)(A + 1) * 513, kBlock)),
+                     dim3(kBlock), 0, cur_stream(), ws.data_ptr<float>(), A,
+                     nsl, (__bf16*)dwa.data_ptr(), (__bf16*)dba.data_ptr(),
                      (__bf16*)dwv.data_ptr(), (__bf16*)dbv.data_ptr());
 }
 
