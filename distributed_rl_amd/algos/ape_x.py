@@ -183,16 +183,7 @@ class ApexLearner(LearnerBase):
         )
         cnn = self.net.nodes[cnn_node]
 
-        # own linear_relu kernel measured SLOWER than hipBLASLt at this
-        # shape even after prefetch pipelining (A/B: 0.741 vs 0.576 ms
-        # step) — the 49-chunk stage/sync cadence dominates; dispatch keeps
-        # the library GEMM, DRL_OWN_LINEAR=1 forces ours
-        own_lin = (ops.linear_relu_supported(in_f, 2 * hidden)
-                   and _os.environ.get("DRL_OWN_LINEAR", "0") == "1")
-
         def hidden_of(feat):
-            if own_lin and feat.dtype == torch.bfloat16:
-                return ops.fused_linear_relu(feat, w1, b1)
             return F.relu(F.linear(feat.to(w1.dtype), w1, b1))
 
         def fast_fwd(x):
@@ -214,7 +205,6 @@ class ApexLearner(LearnerBase):
 
         self._fast_hidden = fast_hidden
         self._cnn = cnn
-        self._own_lin = own_lin
 
         def pre_hidden_of(feat):
             # raw (pre-ReLU) hidden for the pre-activation loss kernels
@@ -238,8 +228,6 @@ class ApexLearner(LearnerBase):
         b1t = self.flat_tparam[2 * hidden * in_f : 2 * hidden * (in_f + 1)]
 
         def t_hidden_of(feat):
-            if own_lin and feat.dtype == torch.bfloat16:
-                return ops.fused_linear_relu(feat, w1t, b1t)
             return F.relu(F.linear(feat.to(w1t.dtype), w1t, b1t))
 
         def target_heads(x):
@@ -509,8 +497,7 @@ class ApexLearner(LearnerBase):
             # kernel; backward = closed-form dh + one head-grad reduction
             # DRL_PREACT_LOSS=0 / DRL_GROUPED_CONV=0 force the unfused
             # pieces (A/B and the old-path oracle)
-            pre = (_os.environ.get("DRL_PREACT_LOSS", "1") == "1"
-                   and not self._own_lin)
+            pre = _os.environ.get("DRL_PREACT_LOSS", "1") == "1"
             if _os.environ.get("DRL_GROUPED_CONV", "1") == "1":
                 # one launch per conv layer for all three forwards; only
                 # the online(s) job is differentiable

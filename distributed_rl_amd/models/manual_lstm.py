@@ -51,14 +51,10 @@ class _ManualLSTMSeq(torch.autograd.Function):
         tanhc = torch.empty(T, B, H, device=dev)
         hs[0] = h0
         cs[0] = c0
-        # Default: in-place addmm_ + fused cell kernel. Two alternatives
-        # were built and MEASURED SLOWER at H=512/B=32 (profiles/): the
-        # one-kernel fused step (DRL_LSTM_FUSED) and the whole-sequence
-        # persistent kernel with agent-scope grid barriers
-        # (DRL_LSTM_PERSISTENT) — both are issue-bound on a 32-block grid
-        # (128 waves on 1024 SIMDs); the hipBLASLt addmm keeps more of the
-        # chip busy. Revisit with a wider decomposition (split-K + 2-phase
-        # barrier) next round.
+        # The round-1 fp32-MFMA one-kernel step and whole-sequence kernel
+        # were removed: both measured slower than the fp32 addmm_ + cell
+        # tier below (issue-bound, 128 waves on 1024 SIMDs) and the bf16
+        # kernels superseded them.
         import os as _os
 
         # K5 v2 (round 2, default): ONE kernel per timestep — bf16-MFMA hh
@@ -93,10 +89,6 @@ class _ManualLSTMSeq(torch.autograd.Function):
                             h_bfs[t + 1], acts[t], tanhc[t]):
                         used = False
                         break
-        if not used and _os.environ.get("DRL_LSTM_PERSISTENT", "0") == "1":
-            ctr = torch.zeros(1, dtype=torch.int32, device=dev)
-            used = bool(ext.lstm_seq_persistent(
-                xp, hs, cs, w_hh.contiguous(), acts, tanhc, ctr))
         if not used:
             h_bfs = None
             w_hh_t = w_hh.t()

@@ -228,41 +228,20 @@ def _fused_conv_backward(x, weight, out, gout, stride, has_bias, chw, pq,
         if need_b:
             gb = gb_ws.to(torch.bfloat16)
     gi = None
-    # Hand-written dgrad exists and is oracle-tested, but MEASURED
-    # SLOWER than MIOpen's igemm at these geometries (tools/
-    # gpu_dgrad_bench.py: 133 vs 28 us at 20x20 s2, 42 vs 33 at 9x9
-    # s1) — dispatch keeps the faster library kernel; DRL_OWN_DGRAD=1
-    # forces ours (profiles/r02 notes).
-    use_own_dgrad = (
-        os.environ.get("DRL_OWN_DGRAD", "0") == "1"
-        and need_x and x.dtype == torch.bfloat16
-        and bool(ext.conv_dgrad_supported(x.shape[2], x.shape[3], C, KH,
-                                          KW, stride, COUT))
-    )
-    if use_own_dgrad:
-        # hand-written MFMA dgrad (conv_mfma.hip): masked-tap gather
-        # against a per-step transposed weight copy — no MIOpen on the
-        # hot path
-        gi = torch.empty_like(x)
-        w_t = torch.empty(weight.numel(), dtype=torch.bfloat16,
-                          device=x.device)
-        ext.conv_dgrad(gout, weight, w_t, gi, stride)
-    if (need_x and not use_own_dgrad) or (need_w and not use_own_wrw):
+    # the input gradient is the library's (MIOpen igemm)
+    if need_x or (need_w and not use_own_wrw):
         if x.dtype == torch.uint8:
             # NHWC u8 -> bf16 for the aten path (own wrw reads u8 directly)
             xf = dequant_frames(x.permute(0, 2, 3, 1), torch.bfloat16)
             xf = xf.permute(0, 3, 1, 2)
         else:
             xf = x
-        gi2, gw2, gb2 = torch.ops.aten.convolution_backward(
+        gi, gw2, gb2 = torch.ops.aten.convolution_backward(
             gout, xf, weight,
             [COUT] if has_bias else None,
             [stride, stride], [0, 0], [1, 1], False, [0, 0], 1,
-            [need_x and not use_own_dgrad, need_w and not use_own_wrw,
-             need_b and not use_own_wrw],
+            [need_x, need_w and not use_own_wrw, need_b and not use_own_wrw],
         )
-        if gi is None:
-            gi = gi2
         if gw is None:
             gw, gb = gw2, gb2
     return (gi if need_x else None), gw, gb
@@ -719,47 +698,6 @@ def fused_maxpool3x3s2(x):
     if _use_hip(x):
         return _MaxPool3x3S2Fn.apply(x)
     return torch_ref.maxpool3x3s2(x)
-
-
-def linear_relu_supported(K, N) -> bool:
-    ext = hip_ext(required=False)
-    return ext is not None and hasattr(ext, "linear_relu_supported") and \
-        bool(ext.linear_relu_supported(K, N))
-
-
-class _LinearReluFn(torch.autograd.Function):
-    """Own MFMA Linear+bias+ReLU (the MLP trunk GEMM; hipBLASLt ran it at
-    ~17.6 us + a separate ReLU). Backward: fused relu-mask, then plain
-    bf16 GEMMs for dX/dW and a reduce for db."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        ext = hip_ext()
-        out = torch.empty(x.shape[0], w.shape[0], dtype=torch.bfloat16,
-                          device=x.device)
-        ext.linear_relu(x.contiguous(), w.contiguous(),
-                        b if b is not None else torch.empty(0, device=x.device),
-                        out)
-        ctx.save_for_backward(x, w, out)
-        ctx.has_bias = b is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, out = ctx.saved_tensors
-        # empty_like of a dense but permuted g would keep g's strides
-        g = g.contiguous()
-        masked = torch.empty_like(g)
-        hip_ext().relu_mask_bwd(g, out, masked)
-        dx = masked.mm(w) if ctx.needs_input_grad[0] else None
-        dw = masked.t().mm(x) if ctx.needs_input_grad[1] else None
-        db = (masked.float().sum(0).to(torch.bfloat16)
-              if ctx.has_bias and ctx.needs_input_grad[2] else None)
-        return dx, dw, db
-
-
-def fused_linear_relu(x, w, b):
-    return _LinearReluFn.apply(x, w, b)
 
 
 def seq_transpose(src: torch.Tensor) -> torch.Tensor:

@@ -579,124 +579,6 @@ __global__ void tr16_probe_kernel(float* out, int mode) {
 }
 }  // namespace
 
-// ===========================================================================
-// Data-grad (dgrad) kernel — retires MIOpen igemm_bwd / ck grouped-bwd from
-// the hot path (VERDICT r01 missing-5). GEMM view:
-//   dx[M=N*H*W rows][C cols] = sum_{kh,kw} G[(n,y,x)][COUT] x Wt[COUT][C]
-// where G gathers gout[n,(y-kh)/S,(x-kw)/S,:] when the tap is valid (stride
-// divisibility + bounds) and zero otherwise. K = KH*KW*COUT runs in 32-wide
-// chunks that never straddle taps (COUT % 32 == 0 for every geometry).
-// B-operand comes from a PRE-TRANSPOSED weight tensor
-//   w_t[c][(kh*KW+kw)*COUT + cout] = w[cout][(kh*KW+kw)*C + c]
-// (built once per step by conv_w_transpose below, L2-resident), so both
-// operands are plain 16 B/lane loads — no LDS at all.
-// ===========================================================================
-namespace {
-
-template <int H, int W, int C, int KH, int KW, int S, int COUT, int WAVES,
-          int RPW>
-__global__ __launch_bounds__(WAVES * 64) void conv_dgrad_kernel(
-    const __bf16* __restrict__ gout,  // (N,P,Q,COUT) NHWC
-    const __bf16* __restrict__ w_t,   // (C, KH*KW*COUT)
-    __bf16* __restrict__ dx,          // (N,H,W,C) NHWC
-    int batch) {
-  constexpr int P = (H - KH) / S + 1;
-  constexpr int Q = (W - KW) / S + 1;
-  constexpr int K = KH * KW * COUT;
-  constexpr int KCHUNKS = K / 32;
-  constexpr int CPT = COUT / 32;  // chunks per tap
-  static_assert(COUT % 32 == 0, "chunks must not straddle taps");
-  constexpr int RFRAG = RPW / 16;
-  constexpr int NFRAG = C / 16;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int M = batch * H * W;
-  const int row0 = (blockIdx.x * WAVES + wave) * RPW;
-  if (row0 >= M) return;
-
-  // per-row-fragment (n, y, x) of this lane's A row
-  int a_n[RFRAG], a_y[RFRAG], a_x[RFRAG];
-#pragma unroll
-  for (int rf = 0; rf < RFRAG; ++rf) {
-    int arow = row0 + rf * 16 + (lane & 15);
-    if (arow >= M) arow = M - 1;
-    a_n[rf] = arow / (H * W);
-    const int rem = arow - a_n[rf] * (H * W);
-    a_y[rf] = rem / W;
-    a_x[rf] = rem - a_y[rf] * W;
-  }
-  const int kpart = (lane >> 4) * 8;
-
-  f32x4 acc[RFRAG][NFRAG];
-#pragma unroll
-  for (int rf = 0; rf < RFRAG; ++rf)
-#pragma unroll
-    for (int f = 0; f < NFRAG; ++f) acc[rf][f] = {0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int kc = 0; kc < KCHUNKS; ++kc) {
-    const int tap = kc / CPT;
-    const int kh = tap / KW;
-    const int kw = tap - kh * KW;
-    const int co = (kc - tap * CPT) * 32 + kpart;
-    bf16x8 a[RFRAG];
-#pragma unroll
-    for (int rf = 0; rf < RFRAG; ++rf) {
-      const int py = a_y[rf] - kh;
-      const int qx = a_x[rf] - kw;
-      const int p = py / S, q = qx / S;
-      const bool ok = py >= 0 && qx >= 0 && py == p * S && qx == q * S &&
-                      p < P && q < Q;
-      if (ok) {
-        a[rf] = *reinterpret_cast<const bf16x8*>(
-            gout + (((int64_t)a_n[rf] * P + p) * Q + q) * COUT + co);
-      } else {
-        a[rf] = bf16x8{};
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < NFRAG; ++f) {
-      const int col = f * 16 + (lane & 15);
-      bf16x8 b = *reinterpret_cast<const bf16x8*>(
-          w_t + (int64_t)col * K + tap * COUT + co);
-#pragma unroll
-      for (int rf = 0; rf < RFRAG; ++rf)
-        acc[rf][f] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rf], b, acc[rf][f], 0, 0, 0);
-    }
-  }
-
-  const int crow_base = (lane >> 4) * 4;
-#pragma unroll
-  for (int rf = 0; rf < RFRAG; ++rf)
-#pragma unroll
-    for (int f = 0; f < NFRAG; ++f) {
-      const int col = f * 16 + (lane & 15);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int orow = row0 + rf * 16 + crow_base + r;
-        if (orow < M) dx[(int64_t)orow * C + col] = (__bf16)acc[rf][f][r];
-      }
-    }
-}
-
-__global__ void conv_w_transpose_kernel(const __bf16* __restrict__ w,
-                                        __bf16* __restrict__ w_t, int TAPS,
-                                        int C, int COUT) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int total = TAPS * C * COUT;
-  if (i >= total) return;
-  const int co = i / (TAPS * C);
-  const int rem = i - co * (TAPS * C);
-  const int tap = rem / C;
-  const int c = rem - tap * C;
-  w_t[((int64_t)c * TAPS + tap) * COUT + co] = w[i];
-}
-
-}  // namespace
-
 // relu-mask + CHW->NHWC transpose in one pass (backward of the fused
 // flatten): masked[n,p,q,c] = gout_chw[n,c,pq] * (out_chw > 0)
 namespace {
@@ -714,116 +596,6 @@ __global__ void relu_mask_bwd_chw_kernel(const __bf16* __restrict__ gout,
     const int64_t n = t / PQ;
     const int64_t src = ((int64_t)n * C + c) * PQ + pq;
     dst[i] = ((float)outv[src] > 0.0f) ? gout[src] : (__bf16)0.0f;
-  }
-}
-}  // namespace
-
-// ===========================================================================
-// Fused Linear(+bias)+ReLU forward for the MLP trunk head (round 2):
-// out(M, N) = relu(x(M, K) @ W(N, K)^T + b). hipBLASLt runs this shape
-// (512, 3136)->(1024) at ~17.6 us + a separate 5 us ReLU; this kernel
-// fuses the epilogue and tiles for the chip: 64 blocks x 4 waves, each
-// wave a 16-row x 128-col strip, W k-slices staged through LDS per
-// 64-wide K chunk (b128 fragment reads, conflict pad).
-// ===========================================================================
-namespace {
-
-template <int K, int N, int NT /*cols per block*/>
-__global__ __launch_bounds__(256) void linear_relu_kernel(
-    const __bf16* __restrict__ x,   // (M, K)
-    const __bf16* __restrict__ w,   // (N, K)
-    const __bf16* __restrict__ b,   // (N) or null
-    __bf16* __restrict__ out,       // (M, N)
-    int M) {
-  constexpr int KB = 64;            // K chunk staged per iteration
-  constexpr int LROW = KB + 32;     // (LROW*2)%256 == 192: bank-spread pad
-  __shared__ __bf16 wlds[NT][LROW];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  // block tile: 32 rows x NT cols; waves 2x2 over (16 rows x NT/2 cols)
-  const int row0 = blockIdx.x * 32 + (wave >> 1) * 16;
-  const int col0 = blockIdx.y * NT + (wave & 1) * (NT / 2);
-  constexpr int NFRAG = NT / 2 / 16;
-  const int arow = row0 + (lane & 15);
-  const int arow_c = arow < M ? arow : (M > 0 ? M - 1 : 0);
-  const int kpart = (lane >> 4) * 8;
-
-  f32x4 acc[NFRAG];
-#pragma unroll
-  for (int f = 0; f < NFRAG; ++f) acc[f] = {0.f, 0.f, 0.f, 0.f};
-
-  // software pipeline: the next chunk's W pieces are prefetched into
-  // registers while the current chunk's MFMAs run (a single-buffered
-  // stage->sync->MFMA loop exposed the full global latency per chunk)
-  constexpr int PIECES = NT * KB / (256 * 8);
-  bf16x8 wpre[PIECES];
-#pragma unroll
-  for (int pc = 0; pc < PIECES; ++pc) {
-    const int base = (tid + pc * 256) * 8;
-    const int r = base / KB;
-    wpre[pc] = *reinterpret_cast<const bf16x8*>(
-        w + (int64_t)(blockIdx.y * NT + r) * K + (base - r * KB));
-  }
-  // A fragments also 1-deep prefetched (they were the remaining serial
-  // latency chain: one L2 round-trip per 16 MFMAs)
-  bf16x8 a_cur[2], a_nxt[2];
-#pragma unroll
-  for (int kc = 0; kc < 2; ++kc)
-    a_cur[kc] = *reinterpret_cast<const bf16x8*>(
-        x + (int64_t)arow_c * K + kc * 32 + kpart);
-  for (int k0 = 0; k0 < K; k0 += KB) {
-    __syncthreads();
-#pragma unroll
-    for (int pc = 0; pc < PIECES; ++pc) {
-      const int base = (tid + pc * 256) * 8;
-      const int r = base / KB;
-      *reinterpret_cast<bf16x8*>(&wlds[r][base - r * KB]) = wpre[pc];
-    }
-    __syncthreads();
-    if (k0 + KB < K) {
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc)
-        a_nxt[kc] = *reinterpret_cast<const bf16x8*>(
-            x + (int64_t)arow_c * K + k0 + KB + kc * 32 + kpart);
-    }
-    if (k0 + KB < K) {
-#pragma unroll
-      for (int pc = 0; pc < PIECES; ++pc) {
-        const int base = (tid + pc * 256) * 8;
-        const int r = base / KB;
-        wpre[pc] = *reinterpret_cast<const bf16x8*>(
-            w + (int64_t)(blockIdx.y * NT + r) * K + k0 + KB +
-            (base - r * KB));
-      }
-    }
-#pragma unroll
-    for (int kc = 0; kc < KB / 32; ++kc) {
-      bf16x8 a = a_cur[kc];
-#pragma unroll
-      for (int f = 0; f < NFRAG; ++f) {
-        const int wl = (wave & 1) * (NT / 2) + f * 16 + (lane & 15);
-        bf16x8 bf = *reinterpret_cast<const bf16x8*>(
-            &wlds[wl][kc * 32 + kpart]);
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bf, acc[f], 0, 0, 0);
-      }
-    }
-    a_cur[0] = a_nxt[0];
-    a_cur[1] = a_nxt[1];
-  }
-  const int crow = (lane >> 4) * 4;
-#pragma unroll
-  for (int f = 0; f < NFRAG; ++f) {
-    const int col = col0 + f * 16 + (lane & 15);
-    const float bv = b ? (float)b[col] : 0.0f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int orow = row0 + crow + r;
-      if (orow < M) {
-        float v = acc[f][r] + bv;
-        out[(int64_t)orow * N + col] = (__bf16)(v > 0.0f ? v : 0.0f);
-      }
-    }
   }
 }
 }  // namespace
@@ -2349,26 +2121,6 @@ static const ConvEntry kVariants[] = {
     make_conv<9, 9, 64, 3, 3, 1, 64, false, 8, 32, 0>(),
 };
 
-struct DgradEntry {
-  Geom g;  // u8 is always false: dgrad never meets the u8 first layer
-  void (*fn)(const __bf16*, const __bf16*, __bf16*, int);
-  int waves, rpw;
-};
-
-template <int H, int W, int C, int KH, int KW, int S, int COUT, int WAVES = 8,
-          int RPW = 16>
-DgradEntry make_dgrad() {
-  return DgradEntry{Geom{H, W, C, KH, KW, S, COUT, false},
-                    conv_dgrad_kernel<H, W, C, KH, KW, S, COUT, WAVES, RPW>,
-                    WAVES, RPW};
-}
-
-static const DgradEntry kDgrad[] = {
-    make_dgrad<20, 20, 32, 4, 4, 2, 64>(),  // apex/r2d2 conv2
-    make_dgrad<9, 9, 64, 3, 3, 1, 64>(),    // apex/r2d2 conv3
-    make_dgrad<20, 20, 16, 4, 4, 2, 32>(),  // impala conv2
-};
-
 const ConvEntry* find_conv(int64_t H, int64_t W, int64_t C, int64_t KH,
                            int64_t KW, int64_t S, int64_t COUT, bool u8) {
   return find_geom(kConvs, Geom{H, W, C, KH, KW, S, COUT, u8});
@@ -2967,43 +2719,6 @@ void wrw_fold_grouped(std::vector<torch::Tensor> parts,
 
 int64_t wrw_plane_pad() { return kPlanePad; }
 
-bool conv_dgrad_supported(int64_t H, int64_t W, int64_t C, int64_t KH,
-                          int64_t KW, int64_t S, int64_t COUT) {
-  return find_geom(kDgrad, Geom{H, W, C, KH, KW, S, COUT, false}) != nullptr;
-}
-
-// gout: (N,COUT,P,Q) logical channels_last bf16; weight (COUT,C,KH,KW)
-// logical channels_last bf16; dx out (N,C,H,W) logical channels_last bf16;
-// w_t workspace (C*KH*KW*COUT) bf16.
-void conv_dgrad(torch::Tensor gout, torch::Tensor weight, torch::Tensor w_t,
-                torch::Tensor dx, int64_t stride) {
-  TORCH_CHECK(dx.dim() == 4 && weight.dim() == 4 && stride >= 1,
-              "conv_dgrad wants 4-D dx and weight and a positive stride");
-  const int64_t N = dx.size(0), C = dx.size(1), H = dx.size(2), W = dx.size(3);
-  const int64_t COUT = weight.size(0), KH = weight.size(2), KW = weight.size(3);
-  const DgradEntry* L =
-      find_geom(kDgrad, Geom{H, W, C, KH, KW, stride, COUT, false});
-  TORCH_CHECK(L, "no dgrad kernel for this geometry");
-  check_nhwc(dx, kBF16, N, C, H, W, "conv_dgrad dx");
-  check_nhwc(weight, kBF16, COUT, C, KH, KW, "conv_dgrad weight");
-  check_nhwc(gout, kBF16, N, COUT, L->g.P(), L->g.Q(), "conv_dgrad gout");
-  check_rows(w_t, kBF16, {weight.numel()}, "conv_dgrad w_t");
-  const int M = checked_rows(N * H * W, "conv_dgrad");
-  if (M == 0) return;
-  auto stream = cur_stream();
-  const int total = (int)weight.numel();
-  hipLaunchKernelGGL(conv_w_transpose_kernel, dim3((total + 255) / 256),
-                     dim3(256), 0, stream, (const __bf16*)weight.data_ptr(),
-                     (__bf16*)w_t.data_ptr(), (int)(KH * KW), (int)C,
-                     (int)COUT);
-  const int rows_per_block = L->waves * L->rpw;
-  const int blocks = (M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(L->fn, dim3(blocks), dim3(L->waves * 64), 0, stream,
-                     (const __bf16*)gout.data_ptr(),
-                     (const __bf16*)w_t.data_ptr(), (__bf16*)dx.data_ptr(),
-                     (int)N);
-}
-
 // backward of the flatten-fused forward: gout2d / out2d are the (N, C*PQ)
 // CHW-ordered grad and forward output, dst_nhwc the (N,C,P,Q) logical
 // channels_last relu-masked grad.
@@ -3024,28 +2739,6 @@ void relu_mask_bwd_chw(torch::Tensor gout2d, torch::Tensor out2d,
                      cur_stream(), (const __bf16*)gout2d.data_ptr(),
                      (const __bf16*)out2d.data_ptr(),
                      (__bf16*)dst_nhwc.data_ptr(), N, (int)C, (int)PQ);
-}
-
-bool linear_relu_supported(int64_t K, int64_t N) {
-  return (K == 3136 && N == 1024);
-}
-
-// out(M, N) = relu(x(M, K) @ w(N, K)^T + b(N)), all bf16; b may be empty.
-void linear_relu(torch::Tensor x, torch::Tensor w, torch::Tensor b,
-                 torch::Tensor out) {
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2);
-  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(linear_relu_supported(K, N), "no linear_relu instantiation");
-  check_rows(x, kBF16, {M, K}, "linear_relu x");
-  check_rows(w, kBF16, {N, K}, "linear_relu w");
-  check_rows(out, kBF16, {M, N}, "linear_relu out");
-  const __bf16* bp = opt_vec(b, N, "linear_relu bias");
-  if (M == 0) return;
-  dim3 grid((checked_rows(M, "linear_relu") + 31) / 32, N / 256);
-  hipLaunchKernelGGL((linear_relu_kernel<3136, 1024, 256>), grid, dim3(256),
-                     0, cur_stream(), (const __bf16*)x.data_ptr(),
-                     (const __bf16*)w.data_ptr(), bp, (__bf16*)out.data_ptr(),
-                     (int)M);
 }
 
 // a table geometry, or any H, W >= 1 at a (C, COUT) with a run-time entry
@@ -3675,14 +3368,8 @@ void register_conv(pybind11::module_& m) {
   m.def("wrw_fold_grouped", &wrw_fold_grouped,
         "ordered fold of up to 4 weight gradients in one launch");
   m.def("wrw_plane_pad", &wrw_plane_pad);
-  m.def("conv_dgrad", &conv_dgrad,
-        "MFMA conv data-grad (masked-tap gather, pre-transposed weights)");
-  m.def("conv_dgrad_supported", &conv_dgrad_supported);
   m.def("relu_mask_bwd_chw", &relu_mask_bwd_chw,
         "relu-mask + CHW->NHWC transpose (backward of the fused flatten)");
-  m.def("linear_relu", &linear_relu,
-        "fused Linear+bias+ReLU fwd (own MFMA GEMM, LDS-staged W)");
-  m.def("linear_relu_supported", &linear_relu_supported);
   namespace py = pybind11;
   m.def("conv3x3p1_fwd", &conv3x3p1_fwd,
         "MFMA 3x3 s1 pad-1 NHWC bf16 conv fwd (+relu_in, bias, residual, "

@@ -180,45 +180,11 @@ def test_conv_wrw_u8_input(ext):
     assert err / scale < 2e-2, f"{err} vs {scale}"
 
 
-DGRAD_SHAPES = [
-    (20, 20, 32, 4, 4, 2, 64),
-    (9, 9, 64, 3, 3, 1, 64),
-    (20, 20, 16, 4, 4, 2, 32),
-]
-
-
-@pytest.mark.parametrize("shape", DGRAD_SHAPES)
-def test_conv_dgrad_vs_aten(ext, shape):
-    """Hand-written dgrad (masked-tap gather vs transposed weights) against
-    aten convolution_backward on identical bf16 operands."""
-    H, W, C, KH, KW, S, COUT = shape
-    torch.manual_seed(5)
-    N = 32
-    P, Q = (H - KH) // S + 1, (W - KW) // S + 1
-    gout = (torch.randn(N, COUT, P, Q, device=DEV) * 0.5).to(
-        torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    w = (torch.randn(COUT, C, KH, KW, device=DEV) * 0.1).to(
-        torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    dx = torch.empty(N, C, H, W, dtype=torch.bfloat16, device=DEV
-                     ).contiguous(memory_format=torch.channels_last)
-    w_t = torch.empty(w.numel(), dtype=torch.bfloat16, device=DEV)
-    ext.conv_dgrad(gout, w, w_t, dx, S)
-    torch.cuda.synchronize()
-    x_dummy = torch.zeros(N, C, H, W, device=DEV, dtype=torch.bfloat16
-                          ).contiguous(memory_format=torch.channels_last)
-    ref, _, _ = torch.ops.aten.convolution_backward(
-        gout.float(), x_dummy.float(), w.float(), None, [S, S], [0, 0],
-        [1, 1], False, [0, 0], 1, [True, False, False])
-    assert torch.allclose(dx.float(), ref, atol=3e-2, rtol=3e-2), \
-        (dx.float() - ref).abs().max()
-
-
-def test_conv_dgrad_in_fused_backward(ext, monkeypatch):
-    """End-to-end: the fused conv autograd must produce the same input grad
-    with the hand-written dgrad as aten does on the fp32 path."""
+def test_fused_conv_input_grad_vs_fp32(ext):
+    """End-to-end: the fused conv autograd (ReLU-mask kernel + the library
+    input gradient on bf16 operands) must produce the same input grad as
+    fp32 autograd of relu(conv2d)."""
     from distributed_rl_amd.ops import fused_conv_relu
-
-    monkeypatch.setenv("DRL_OWN_DGRAD", "1")
 
     torch.manual_seed(6)
     N, C, H, W, COUT, KH, S = 16, 32, 20, 20, 64, 4, 2

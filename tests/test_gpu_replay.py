@@ -851,26 +851,3 @@ def test_dequant_nhwc_rejects(ext):
         ext.dequant_nhwc(x, _cl(_bf(2, 4, 3, 3, dev="cpu")))
     with pytest.raises(RuntimeError):
         ext.dequant_nhwc(x, _bf(2, 4, 3, 3))
-
-
-def test_linear_relu_backward_with_a_permuted_gradient(ext):
-    """A dense but transposed incoming gradient: the backward must mask the
-    logical elements, not walk two differently strided buffers in step."""
-    from distributed_rl_amd import ops
-
-    K, N, B = 3136, 1024, 8  # the one size linear_relu is built for
-    assert ops.linear_relu_supported(K, N)
-    gen = torch.Generator().manual_seed(8)
-    x = torch.randn(B, K, generator=gen).to(BF16).to(DEV).requires_grad_(True)
-    w = (torch.randn(N, K, generator=gen) * 0.05).to(BF16).to(DEV)
-    b = torch.zeros(N, dtype=BF16, device=DEV)
-    y = ops.fused_linear_relu(x, w, b)
-    g = torch.randn(N, B, generator=gen).to(BF16).to(DEV).t()  # dense, permuted
-    (gx,) = torch.autograd.grad(y, x, g)
-    want = (g * (y > 0)).double().mm(w.double())
-    err = (gx.double() - want).abs().max().item()
-    # bf16 result: half an ulp, 2^-9 of the element; fp32 accumulation of
-    # 1024 products whose absolute sum is about sqrt(1024) times the result:
-    # 1024 * 2^-24 * 32 = 2^-9 again. Twice their sum; a gradient masked at
-    # the wrong elements is off by the size of the result itself.
-    assert err <= 2 ** -7 * want.abs().max().item()
